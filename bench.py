@@ -9,8 +9,15 @@ Workload (BASELINE.json configs[2], the config the metric is quoted on):
 1024 agents per GPU, N=30, 2-D double integrator (nx=4, nu=2), nb=2 neighbours,
 fp64 — weak scaling (1024 agents per rank; the 4096-agent cfg4 at 4 GPUs).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure
+with its roofline arithmetic from the committed counter summaries).  --full adds what takes runs
+of its own: the CPU baseline, the cfg5 sub-object, the reference configuration (N = 125, LPV
+rounds, the osqp_solve_qp drop-in) and the fp32 path's check against the fp64 solve; --no-cpu,
+--no-ref and --no-cfg5 drop parts of it.  --dump-outputs DIR writes what the last timed step
+computed (DIR/<name>.npy) so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -40,18 +47,28 @@ def main():
                          "integrator (nx=6, nu=3) on the fp64 stage-wise Riccati kernel")
     ap.add_argument("--fp32", action="store_true",
                     help="cfg5 only: BASELINE cfg5's fp32 path (the Riccati kernel's fp32 mode: an fp32 Riccati "
-                         "factorisation, fp64 iterates / residuals, tol 1e-6), checked against the fp64 solve")
+                         "factorisation, fp64 iterates / residuals, tol 1e-6); --full checks it against the fp64 "
+                         "solve")
     ap.add_argument("--agents", type=int, default=None, help="agents per GPU (default: the config's)")
     ap.add_argument("--agents-total", type=int, default=None,
                     help="strong scaling: this many agents in all, split evenly over the ranks (BASELINE cfg4: "
                          "--agents-total 4096 on 8 GPUs); default: weak scaling, --agents per GPU")
     ap.add_argument("--horizon", type=int, default=None)
     ap.add_argument("--nb", type=int, default=2)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-ref", action="store_true", help="skip the reference-configuration (N=125) line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the cfg5 sub-object, "
+                         "the reference configuration (N=125, LPV rounds, osqp_solve_qp drop-in) and, with --fp32, "
+                         "the check against the fp64 solve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (z, kkt, iters, status, the "
+                         "advanced x0 / u_prev, the exchanged trajectories) as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: target CPU-baseline sample time")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-ref", action="store_true",
+                    help="--full without the reference-configuration (N=125) line")
     ap.add_argument("--no-cfg5", action="store_true",
-                    help="skip the cfg5 sub-object of the default line (BASELINE configs[4]: fp64 and fp32 paths)")
+                    help="--full without the cfg5 sub-object of the default line (BASELINE configs[4]: fp64 and "
+                         "fp32 paths)")
     args = ap.parse_args()
     cfg5 = args.config == "cfg5"
     if args.fp32 and not cfg5:
@@ -119,6 +136,12 @@ def main():
         R.step(timer=ev[k])
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what a caller of R.step() holds after the last timed step: the solver's outputs, the state
+        # the advance left for the next round and the exchanged trajectories of every agent
+        dump_outputs(args.dump_outputs, "" if rank == 0 else f"_rank{rank}",
+                     {"z": R.z, "kkt": R.kkt, "iters": R.iters, "status": R.status, "x0": R.x0, "u_prev": R.u_prev,
+                      "traj_all": R.traj_all})
     iters_sum = hist_it.to(torch.float64).sum()
     kkt_max = hist_kkt.max()
     # unsolved: neither solved nor solved-inaccurate (OSQP status_val 1 / 2)
@@ -146,17 +169,19 @@ def main():
     pmc_kind = ("cfg5fp32" if args.fp32 else "cfg5") if cfg5 else None
     traffic, traffic_src = pmc_traffic(pmc_kind)
     peak = FP32_PEAK_TFLOPS if args.fp32 else FP64_PEAK_TFLOPS
-    fp32_check = fp32_vs_fp64(R) if (args.fp32 and rank == 0) else None
+    # everything below that takes runs of its own is --full's; a plain run prints the timed loop's line
+    fp32_check = fp32_vs_fp64(R) if (args.full and args.fp32 and rank == 0) else None
 
     cpu = None
     max_err = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    solo = args.full and rank == 0 and world == 1
+    if solo and not args.no_cpu:
         cpu, max_err = cpu_baseline(R, args.cpu_seconds, rounds=1 if cfg5 else 4, newton=3 if cfg5 else 0,
                                     label=args.config)
     ref_line = osqp_line = cfg5_sub = None
-    if rank == 0 and world == 1 and not args.no_cfg5 and not cfg5 and not strong:
+    if solo and not args.no_cfg5 and not cfg5 and not strong:
         cfg5_sub = cfg5_line(ctx)
-    if rank == 0 and world == 1 and not args.no_ref and not cfg5:
+    if solo and not args.no_ref and not cfg5:
         ref_line = reference_config(ctx)
         ref_line["lpv_rounds"] = lpv_rounds(ctx)
         ref_line["lpv_rounds_finish"] = lpv_rounds(ctx, finish=True, check=False)
@@ -170,6 +195,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
@@ -229,6 +255,28 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_CAP_BYTES = 60 * 10**6   # of array data; the .npy headers stay well inside the 64 MB the dump may take
+
+
+def dump_outputs(path, suffix, tensors, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: each device tensor as path/<name><suffix>.npy in float64 (the solver's
+    precision; the int32 counters are exact in it).  At most `cap` bytes of array data in all: where
+    the arrays are larger, each keeps a fixed seeded sample of its leading-axis rows (the same rows
+    in every run of the same arguments) in proportion to its size, and the kept row indices go to
+    <name>_rows<suffix>.npy inside the same cap."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: t.detach().to("cpu").numpy().astype(np.float64) for k, t in tensors.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in arrs.items():
+        if total > cap:
+            row = a.nbytes // a.shape[0] + 8   # a kept row and its index
+            keep = max(1, min(a.shape[0], int(cap * (a.nbytes / total)) // row))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(path, f"{k}_rows{suffix}.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
 
 
 def cfg5_line(ctx, steps=10, warmup=2):

@@ -9,9 +9,9 @@ cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/$TAG
 O=gpurun_out/$TAG
 export TMPDIR=/tmp
-BENCH="bench.py --steps 100 --warmup 5"
-C5="bench.py --config cfg5 --steps 10 --warmup 2"
-C5F="bench.py --config cfg5 --fp32 --steps 10 --warmup 2"
+BENCH="bench.py --full --steps 100 --warmup 5"
+C5="bench.py --full --config cfg5 --steps 10 --warmup 2"
+C5F="bench.py --full --config cfg5 --fp32 --steps 10 --warmup 2"
 timeout -k 10 600 python -u -m pytest tests -m gpu -q -rA -p no:cacheprovider --timeout 280 --timeout-method thread > $O/pytest_gpu.log 2>&1 &&
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
 timeout -k 10 600 python $BENCH > $O/bench.json 2> $O/bench.err &&
