@@ -197,6 +197,7 @@ SIGNATURES = {
     "cmpc_ocd_converged_dev": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_double, _DP, _DP, _IP,
                                           ct.c_void_p]),
     "cmpc_selftest_mfma": (ct.c_int, [ct.c_void_p, _DP, _DP, _DP]),
+    "cmpc_selftest_fma_bcast": (ct.c_int, [ct.c_void_p, _DP, _DP, _DP, _DP, _DP]),
     "cmpc_lpv_build_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lpv_params), ct.POINTER(cmpc_track),
                                       ct.POINTER(cmpc_lpv_dims), ct.POINTER(cmpc_lpv_data),
                                       ct.POINTER(cmpc_lpv_build_out), ct.c_void_p]),

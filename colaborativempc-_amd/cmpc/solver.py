@@ -157,3 +157,16 @@ def selftest_mfma(ctx=None, seed=0):
     D = np.zeros((16, 16))
     ctx.check(ctx.lib.cmpc_selftest_mfma(ctx.h, L.dptr(A), L.dptr(B), L.dptr(D)))
     return D, A @ B
+
+
+def selftest_fma_bcast(A, X, C, ctx=None):
+    """The fused row-broadcast fma against the two-instruction expression on one wavefront.
+
+    A, X, C: 64 doubles (one per lane).  Returns (fused, ref), each [4][16][64] (case, broadcast
+    lane J, lane); cases as in cmpc.h.  The two must be equal bit for bit."""
+    ctx = ctx or L.default_context()
+    A, X, C = (np.ascontiguousarray(v, dtype=np.float64).reshape(64) for v in (A, X, C))
+    fused = np.zeros((4, 16, 64))
+    ref = np.zeros((4, 16, 64))
+    ctx.check(ctx.lib.cmpc_selftest_fma_bcast(ctx.h, L.dptr(A), L.dptr(X), L.dptr(C), L.dptr(fused), L.dptr(ref)))
+    return fused, ref

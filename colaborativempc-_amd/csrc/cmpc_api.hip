@@ -609,4 +609,34 @@ int cmpc_selftest_mfma(cmpc_ctx* ctx, const double* A, const double* B, double* 
     return CMPC_OK;
 }
 
+int cmpc_selftest_fma_bcast(cmpc_ctx* ctx, const double* A, const double* X, const double* C, double* fused,
+                            double* ref) {
+    if (!ctx || !A || !X || !C || !fused || !ref) return CMPC_ERR_ARG;
+    int rc = set_device(ctx);
+    if (rc != CMPC_OK) return rc;
+    const size_t no = 4 * 16 * 64;
+    char* base = arena(ctx, 8 * (5 * 64 + 2 * no) + 1024);
+    if (!base) return fail(ctx, CMPC_ERR_NOMEM, "arena");
+    Carve cv{base};
+    double *dA = cv.take<double>(64), *dX = cv.take<double>(64), *dC = cv.take<double>(64);
+    double *d1 = cv.take<double>(64), *dz = cv.take<double>(64);
+    double *dF = cv.take<double>(no), *dR = cv.take<double>(no);
+    double h1[64], hz[64];
+    for (int i = 0; i < 64; ++i) {
+        h1[i] = 1.0;
+        hz[i] = -0.0;
+    }
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dA, A, 8 * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dX, X, 8 * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dC, C, 8 * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d1, h1, 8 * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dz, hz, 8 * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(cmpc::selftest_fma_bcast_launch(dA, dX, dC, d1, dz, dF, dR, s));
+    HIP_TRY(hipMemcpyAsync(fused, dF, 8 * no, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ref, dR, 8 * no, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
 }  // extern "C"

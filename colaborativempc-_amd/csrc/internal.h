@@ -261,6 +261,8 @@ hipError_t di_advance_launch(const DiConst& c, const double* z, double* x0, doub
                              hipStream_t s);
 
 hipError_t selftest_mfma_launch(const double* A, const double* B, double* D, hipStream_t s);
+hipError_t selftest_fma_bcast_launch(const double* A, const double* X, const double* C, const double* one,
+                                     const double* nzero, double* fused, double* ref, hipStream_t s);
 
 // OCD coupling-dual round (ocd.hip).
 struct OcdConst {

@@ -213,10 +213,11 @@ __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double
     };
     auto step = [&](int k, const double* av, const double* bv) __attribute__((always_inline)) {
         double v0 = bv[0], v1 = 0.0;
+        const double xs = dpp_settled(xr);
         static_for<0, NA>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) v1 = fma(av[tt], bcast16<tt>(xr), v1);
-            else v0 = fma(av[tt], bcast16<tt>(xr), v0);
+            if constexpr (tt & 1) v1 = fma_bcast16s<tt>(av[tt], xs, v1);
+            else v0 = fma_bcast16s<tt>(av[tt], xs, v0);
         });
         if constexpr (LS) xr = (v0 + v1) + xr;  // x_{k+1} = x_k + D_k x_k + B_k u_k
         else xr = v0 + v1;
@@ -263,9 +264,10 @@ __device__ __forceinline__ void phi_build(int l, int N, const double* A, double*
         static_for<0, NX>([&](auto c_c) __attribute__((always_inline)) {
             constexpr int cc = decltype(c_c)::value;
             double v = 0.0;
+            const double ps = dpp_settled(ph[cc]);
             static_for<0, NX>([&](auto t_c) __attribute__((always_inline)) {
                 constexpr int tt = decltype(t_c)::value;
-                v = fma(ar[tt], bcast16<tt>(ph[cc]), v);
+                v = fma_bcast16s<tt>(ar[tt], ps, v);
             });
             nw[cc] = v;
         });
@@ -312,10 +314,11 @@ __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const dou
         double v0 = 0.0, v1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NU; ++j) v0 = fma(av[NX + j], av[NX + NU + j], v0);
+        const double xs = dpp_settled(xr);
         static_for<0, NX>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) v1 = fma(av[tt], bcast16<tt>(xr), v1);
-            else v0 = fma(av[tt], bcast16<tt>(xr), v0);
+            if constexpr (tt & 1) v1 = fma_bcast16s<tt>(av[tt], xs, v1);
+            else v0 = fma_bcast16s<tt>(av[tt], xs, v0);
         });
         xr = (a + i < e) ? v0 + v1 : xr;
         X[(k + 1) * NX + s] = xr;
@@ -391,9 +394,10 @@ __device__ __forceinline__ void psi_build(int l, int N, const double* A, double*
         static_for<0, NX>([&](auto c_c) __attribute__((always_inline)) {
             constexpr int cc = decltype(c_c)::value;
             double v = 0.0;
+            const double ts = dpp_settled(tr[cc]);
             static_for<0, NX>([&](auto t_c) __attribute__((always_inline)) {
                 constexpr int tt = decltype(t_c)::value;
-                v = fma(at[tt], bcast16<tt>(tr[cc]), v);
+                v = fma_bcast16s<tt>(at[tt], ts, v);
             });
             nw[cc] = v;
         });
@@ -424,10 +428,11 @@ __device__ __forceinline__ void psi3seg(int l, int N, const double* A, double* y
     auto step = [&](int i, const double* av) __attribute__((always_inline)) {
         const int k = e - 1 - i >= b ? e - 1 - i : b;
         double p0 = av[NX], p1 = 0.0;
+        const double ps = dpp_settled(pr);
         static_for<0, NX>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) p1 = fma(av[tt], bcast16<tt>(pr), p1);
-            else p0 = fma(av[tt], bcast16<tt>(pr), p0);
+            if constexpr (tt & 1) p1 = fma_bcast16s<tt>(av[tt], ps, p1);
+            else p0 = fma_bcast16s<tt>(av[tt], ps, p0);
         });
         pr = (e - 1 - i >= b) ? p0 + p1 : pr;
         y[k * NX + s] = pr;
@@ -504,17 +509,13 @@ __device__ __forceinline__ void psi3(int l, int N, const double* A, double* y0, 
         yv = y[k * NX + sx];
     };
     auto step = [&](int k, const double* av, double yk) __attribute__((always_inline)) {
-        double ps[NX];
+        double p0 = LS ? 0.0 : yk, p1 = 0.0;
+        const double ps = dpp_settled(pr);
         static_for<0, NX>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            ps[tt] = bcast16<tt>(pr);
+            if constexpr (tt & 1) p1 = fma_bcast16s<tt>(av[tt], ps, p1);
+            else p0 = fma_bcast16s<tt>(av[tt], ps, p0);
         });
-        double p0 = LS ? 0.0 : yk, p1 = 0.0;
-#pragma unroll
-        for (int t = 0; t < NX; ++t) {
-            if (t & 1) p1 = fma(av[t], ps[t], p1);
-            else p0 = fma(av[t], ps[t], p0);
-        }
         if constexpr (LS) pr = fma(dmask, p0 + p1, yk + pr);
         else pr = p0 + p1;
         y[k * NX + sx] = pr;
@@ -1452,9 +1453,11 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     const double lj = rw[j] * y;
                     rw[j] = lj;
                     if constexpr (j + 1 < 16) dn = fma(-lj, lj, rw[j + 1]);
+                    // (the trailing updates read l through one nop; the pivot chain above does not)
+                    const double ls = dpp_settled(lj);
                     static_for<j + 1, 16>([&](auto cc) __attribute__((always_inline)) {
                         constexpr int c2 = decltype(cc)::value;
-                        rw[c2] = fma(-lj, bcast16<c2>(lj), rw[c2]);
+                        rw[c2] = fnma_bcast16s<c2>(lj, ls, rw[c2]);
                     });
                     // (no scheduling barrier: the next pivot overlaps this one's trailing updates)
                 });
@@ -1482,12 +1485,13 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                         const double dcc = bcast16<cc>(inv_own);
                         const double lcc = (i16 > cc) ? rw[cc] * dcc : 0.0;
 #pragma unroll
-                        for (int I = J + 1; I < T; ++I)
+                        for (int I = J + 1; I < T; ++I) {
+                            // (a tile's four values behind one nop; each is its own addend)
+                            const v4d vs = dpp_settled(acc[I * (I + 1) / 2 + J]);
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const double v = acc[I * (I + 1) / 2 + J][r];
-                                acc[I * (I + 1) / 2 + J][r] = fma(-bcast16<cc>(v), lcc, v);
-                            }
+                            for (int r = 0; r < 4; ++r)
+                                acc[I * (I + 1) / 2 + J][r] = fnma_bcast16s<cc>(lcc, vs[r], vs[r]);
+                        }
                     });
 #pragma unroll
                     for (int I = J + 1; I < T; ++I)
@@ -1669,9 +1673,10 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 if ((l >> 4) == J) rv = vb[J * 16 + (l & 15)] - (J > 0 ? red[l & 15] : 0.0);
                 {  // y_J = L_JJ^{-1} r_J: row J broadcasts its lanes, four independent fma chains
                     double y4[4] = {0.0, 0.0, 0.0, 0.0};
+                    const double rs = dpp_settled(rv);
                     static_for<0, 16>([&](auto jc) __attribute__((always_inline)) {
                         constexpr int cc = decltype(jc)::value;
-                        y4[cc & 3] = fma(Lr[cc], bcast16<cc>(rv), y4[cc & 3]);
+                        y4[cc & 3] = fma_bcast16s<cc>(Lr[cc], rs, y4[cc & 3]);
                     });
                     rv = (y4[0] + y4[1]) + (y4[2] + y4[3]);
                 }
@@ -1694,9 +1699,10 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 double rv = ((l >> 4) == J) ? vb[J * 16 + (l & 15)] - p : 0.0;
                 {  // x_J = L_JJ^{-T} r_J
                     double x4[4] = {0.0, 0.0, 0.0, 0.0};
+                    const double rs = dpp_settled(rv);
                     static_for<0, 16>([&](auto jc) __attribute__((always_inline)) {
                         constexpr int cc = decltype(jc)::value;
-                        x4[cc & 3] = fma(Lc[cc], bcast16<cc>(rv), x4[cc & 3]);
+                        x4[cc & 3] = fma_bcast16s<cc>(Lc[cc], rs, x4[cc & 3]);
                     });
                     rv = (x4[0] + x4[1]) + (x4[2] + x4[3]);
                 }

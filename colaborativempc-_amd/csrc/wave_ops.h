@@ -74,6 +74,82 @@ __device__ __forceinline__ double bcast16(double x) {
     return __builtin_amdgcn_update_dpp(0.0, x, 0x150 + J, 0xF, 0xF, true);
 }
 
+// fma(a, bcast16<J>(x), c) and fma(-bcast16<J>(x), a, c) as one instruction: v_fmac_f64 is the one
+// fp64 operation that takes a DPP source (row_newbcast only), which the compiler never forms from
+// the two-instruction expression.  Same single-rounded fma on the same operands, so the bits are
+// those of the expression (-DCMPC_NO_FMA_BCAST expands to it: A/B builds, the self-test's
+// reference).  Same calling rule as bcast16: whole wave active.
+// The compiler's hazard recognizer does not see inside the asm, so the two wait states the ISA
+// asks for between a VALU write of x and its DPP read are the caller's:
+//  fma_bcast16 / fnma_bcast16    carry them (a leading s_nop 1, which also covers a
+//                                transcendental result read by the next VALU instruction): safe on
+//                                any x.  The nop costs as much as the instruction (DESIGN, cost
+//                                table), so this form is for a source used once.
+//  fma_bcast16s / fnma_bcast16s  the bare instruction, for an x that went through dpp_settled():
+//                                one nop for every broadcast of that source.  The data dependence
+//                                orders write -> nop -> read; what it cannot exclude is a register
+//                                copy of x that the allocator places directly before a read, so
+//                                each build's assembly is checked (tools/check_dpp_hazards.py,
+//                                which also covers a compiler-emitted DPP read of a fused result).
+#ifdef CMPC_NO_FMA_BCAST
+constexpr bool kFmaBcast = false;
+#else
+constexpr bool kFmaBcast = true;
+#endif
+template <class V>
+__device__ __forceinline__ V dpp_settled(V x) {  // V: double, or v4d (four values behind one nop)
+    if constexpr (kFmaBcast) asm("s_nop 1" : "+v"(x));
+    return x;
+}
+template <int J>
+__device__ __forceinline__ double fma_bcast16(double a, double x, double c) {
+    static_assert(J >= 0 && J < 16, "row_newbcast lane");
+    if constexpr (kFmaBcast) {
+        asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(c)
+            : "v"(x), "v"(a), "n"(J));
+        return c;
+    } else {
+        return fma(a, bcast16<J>(x), c);
+    }
+}
+template <int J>
+__device__ __forceinline__ double fnma_bcast16(double a, double x, double c) {
+    static_assert(J >= 0 && J < 16, "row_newbcast lane");
+    if constexpr (kFmaBcast) {
+        asm("s_nop 1\n\tv_fmac_f64_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(c)
+            : "v"(x), "v"(a), "n"(J));
+        return c;
+    } else {
+        return fma(-bcast16<J>(x), a, c);
+    }
+}
+template <int J>
+__device__ __forceinline__ double fma_bcast16s(double a, double x, double c) {
+    static_assert(J >= 0 && J < 16, "row_newbcast lane");
+    if constexpr (kFmaBcast) {
+        asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(c)
+            : "v"(x), "v"(a), "n"(J));
+        return c;
+    } else {
+        return fma(a, bcast16<J>(x), c);
+    }
+}
+template <int J>
+__device__ __forceinline__ double fnma_bcast16s(double a, double x, double c) {
+    static_assert(J >= 0 && J < 16, "row_newbcast lane");
+    if constexpr (kFmaBcast) {
+        asm("v_fmac_f64_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(c)
+            : "v"(x), "v"(a), "n"(J));
+        return c;
+    } else {
+        return fma(-bcast16<J>(x), a, c);
+    }
+}
+
 // 1/sqrt(x) to full double precision: hardware estimate + two Newton steps.
 __device__ __forceinline__ double rsqrt_d(double x) {
     double y = __builtin_amdgcn_rsq(x);

@@ -525,6 +525,14 @@ int cmpc_comm_destroy(cmpc_ctx* ctx);
  * (D = A*B for one 16x16x4 tile, A,B host 16x4 / 4x16 row-major, D host 16x16). */
 int cmpc_selftest_mfma(cmpc_ctx* ctx, const double* A, const double* B, double* D);
 
+/* Device self-test of the fused row-broadcast fma the v3 kernel uses (v_fmac_f64 with a DPP
+ * row_newbcast source) against the two-instruction expression, on one wavefront.  A, X, C: host,
+ * 64 doubles (one per lane).  fused, ref: host, [4][16][64] doubles: case, broadcast lane J, lane.
+ * Cases: 0  fma(A, bcast_J(X), C);  1  fma(-bcast_J(X), A, C);  2  as 0 and 3  fma(-bcast_J(X), A, X),
+ * both through the settled-source form.  The two arrays must be equal bit for bit. */
+int cmpc_selftest_fma_bcast(cmpc_ctx* ctx, const double* A, const double* X, const double* C, double* fused,
+                            double* ref);
+
 #ifdef __cplusplus
 }
 #endif

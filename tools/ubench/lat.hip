@@ -11,7 +11,6 @@ __device__ __forceinline__ unsigned long long stamp() {
   __builtin_amdgcn_sched_barrier(0);
   return t;
 }
-__device__ __forceinline__ void wsync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); asm volatile("" ::: "memory"); }
 constexpr int NX = 4, NU = 2, N = 30;
 
 // (a) readlane-broadcast forward recursion (current kernels)
@@ -288,6 +287,48 @@ __global__ __launch_bounds__(64,1) void k_dpp(const double* gA, double* out, uns
   if (l == 0) cyc[blockIdx.x] = (t1 - t0);
   out[blockIdx.x * 64 + l] = v;
 }
+// fused broadcast-fma (v_fmac_f64_dpp row_newbcast, cmpc::fma_bcast16) against the pair
+// v_mov_b64_dpp + v_fmac_f64: dependent chain of 32 (each broadcast reads the previous result)
+__global__ __launch_bounds__(64,1) void k_dpp_fused(const double* gA, double* out, unsigned long long* cyc) {
+  int l = threadIdx.x;
+  double v = gA[l];
+  unsigned long long t0 = stamp();
+#pragma unroll
+  for (int i = 0; i < 32; ++i) v = cmpc::fma_bcast16<3>(0.5, v, v);
+  asm volatile("v_mov_b64 %0, %0" : "+v"(v));
+  unsigned long long t1 = stamp();
+  if (l == 0) cyc[blockIdx.x] = (t1 - t0);
+  out[blockIdx.x * 64 + l] = v;
+}
+// ... and 32 independent accumulators, 16 rounds, the broadcast source written long before.
+// MODE 0: the pair; 1: fma_bcast16 (each carries its s_nop 1); 2: dpp_settled once per source and
+// round, then fma_bcast16s (one nop per 16 broadcasts: the triangular solves' shape)
+template <int MODE>
+__global__ __launch_bounds__(64,1) void k_dpp_tp(const double* gA, double* out, unsigned long long* cyc) {
+  int l = threadIdx.x;
+  double x[32];
+  for (int q = 0; q < 32; ++q) x[q] = gA[l] + q;
+  // two sources, opaque per round: the pair's broadcasts can be neither hoisted nor shared
+  double y0 = gA[64 + l] * 1e-3, y1 = gA[128 + l] * 1e-3, a = 0.5;
+  unsigned long long t0 = stamp();
+  for (int rep = 0; rep < 16; ++rep) {
+    asm volatile("s_nop 4" : "+v"(y0), "+v"(y1), "+v"(a));
+    const double s0 = cmpc::dpp_settled(y0), s1 = cmpc::dpp_settled(y1);
+    static_for<0, 32>([&](auto qc) __attribute__((always_inline)) {
+      constexpr int q = decltype(qc)::value;
+      const double y = q < 16 ? (MODE == 2 ? s0 : y0) : (MODE == 2 ? s1 : y1);
+      if constexpr (MODE == 0) x[q] = fma(a, cmpc::bcast16<q & 15>(y), x[q]);
+      else if constexpr (MODE == 1) x[q] = cmpc::fma_bcast16<q & 15>(a, y, x[q]);
+      else x[q] = cmpc::fma_bcast16s<q & 15>(a, y, x[q]);
+    });
+  }
+  double s = 0;
+  for (int q = 0; q < 32; ++q) s += x[q];
+  asm volatile("v_mov_b64 %0, %0" : "+v"(s));
+  unsigned long long t1 = stamp();
+  if (l == 0) cyc[blockIdx.x] = (t1 - t0);
+  out[blockIdx.x * 64 + l] = s;
+}
 int main() {
   const int nb = 1024;
   std::vector<double> hA(N*NX*NX*1 + 4096), hK(256);
@@ -312,6 +353,10 @@ int main() {
     hipLaunchKernelGGL(k_mfma_tp, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("mfma f64 throughput (10 indep, drained)", 320);
     hipLaunchKernelGGL(k_fma_tp, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("fma f64 throughput (16 indep)", 512);
     hipLaunchKernelGGL(k_dpp, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("dpp bcast -> fma dep chain", 32);
+    hipLaunchKernelGGL(k_dpp_fused, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("fused dpp-fma dep chain", 32);
+    hipLaunchKernelGGL(k_dpp_tp<0>, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("dpp bcast + fma pair throughput (32 indep)", 512);
+    hipLaunchKernelGGL(k_dpp_tp<1>, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("fused dpp-fma throughput (32 indep, s_nop 1)", 512);
+    hipLaunchKernelGGL(k_dpp_tp<2>, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("fused dpp-fma throughput (32 indep, settled source: one nop per 16)", 512);
     hipLaunchKernelGGL(k_fma, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("fma f64 dep chain", 64);
     hipLaunchKernelGGL(k_lds, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("lds dep read", 32);
     hipLaunchKernelGGL(k_readlane, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("readlane_d->fma dep", 32);
