@@ -14,7 +14,8 @@
 // in a per-problem global-memory workspace (column-major, coalesced over rows), followed by
 // iterative refinement against the unregularised system.  Rows of Aeq / A that are entirely
 // zero are dropped (0 = 0 rows of the reference's QP, LPV_Planner.py:445-447), or flag the
-// problem infeasible when their right-hand side cannot hold.
+// problem infeasible when their right-hand side cannot hold.  A bound that no point can meet
+// (b_r, ub_i = -inf, lb_i = +inf) flags it infeasible too.
 #include <cmath>
 
 #include "internal.h"
@@ -26,7 +27,7 @@ namespace {
 constexpr int kQpThreads = 256;
 
 struct QpWs {  // offsets (doubles) into one problem's workspace
-    int K, x, y, t, lam, act, rd, re, rp, th, rho, dx, dy, gdx, rhs, sol, res, tmp, bx, by, dsc, rsa, rse, total;
+    int K, x, y, t, lam, act, rd, re, rp, th, rho, dx, dy, gdx, rhs, sol, res, tmp, bx, by, bt, bl, dsc, rsa, rse, total;
 };
 
 __host__ __device__ inline int mi_of(int m, int n) { return m - 2 * n; }
@@ -60,6 +61,8 @@ __host__ __device__ inline QpWs qp_ws_layout(int n, int me, int m) {
     w.tmp = take(nk > m ? nk : m);
     w.bx = take(n);
     w.by = take(me);
+    w.bt = take(m);
+    w.bl = take(m);
     w.dsc = take(n);
     w.rsa = take(mi_of(m, n));
     w.rse = take(me);
@@ -129,6 +132,7 @@ __global__ __launch_bounds__(kQpThreads) void qp_dense_kernel(const QpConst c, c
     double *rd = ws + L.rd, *re = ws + L.re, *rp = ws + L.rp, *th = ws + L.th, *rho = ws + L.rho;
     double *dx = ws + L.dx, *dy = ws + L.dy, *gdx = ws + L.gdx, *rhs = ws + L.rhs, *sol = ws + L.sol;
     double *res = ws + L.res, *tmp = ws + L.tmp, *bx = ws + L.bx, *by = ws + L.by;
+    double *bt = ws + L.bt, *bl = ws + L.bl;
     double *dsc = ws + L.dsc, *rsa = ws + L.rsa, *rse = ws + L.rse;
     const double* H = P.H + (size_t)pb * n * n;
     const double* f = P.f + (size_t)pb * n;
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(kQpThreads) void qp_dense_kernel(const QpConst c, c
                 if (h < 0.0) bad_l = 1;
             }
         }
-        if (!(h == h)) bad_l = 1;  // NaN bound
+        if (!(h == h) || h == -INFINITY) bad_l = 1;  // NaN bound, or one that no point meets
         act[r] = a;
     }
     for (int r = tid; r < me; r += kQpThreads) {
@@ -296,6 +300,10 @@ __global__ __launch_bounds__(kQpThreads) void qp_dense_kernel(const QpConst c, c
             res_p_best = res_p;
             for (int i = tid; i < n; i += kQpThreads) bx[i] = x[i];
             for (int i = tid; i < me; i += kQpThreads) by[i] = y[i];
+            for (int r = tid; r < m; r += kQpThreads) {
+                bt[r] = t[r];
+                bl[r] = lam[r];
+            }
         }
         if (merit < c.tol) {
             stop = kStopConverged;
@@ -501,12 +509,19 @@ __global__ __launch_bounds__(kQpThreads) void qp_dense_kernel(const QpConst c, c
         if (best_it > 0) {
             for (int i = tid; i < n; i += kQpThreads) x[i] = bx[i];
             for (int i = tid; i < me; i += kQpThreads) y[i] = by[i];
+            for (int r = tid; r < m; r += kQpThreads) {
+                t[r] = bt[r];
+                lam[r] = bl[r];
+            }
             __syncthreads();
         }
-        // quadprog exit flags: 1 converged, 0 iteration cap, -2 infeasible, -3 unbounded, -6 nonconvex
+        // quadprog exit flags: 1 converged, 0 iteration cap, -2 infeasible, -3 unbounded, -6 nonconvex.
+        // A solve the cap cut off while its merit was still improving (a new best within the last
+        // kStallIters iterations) is 0; one that had stopped improving is judged by what it could not reduce.
         if (bad) flag = -2;
         else if (nonconvex_diag || indefinite) flag = -6;
         else if (best_m < 1e3 * c.tol) flag = 1;  // converged to the attainable accuracy (reported in output)
+        else if (stop == kStopMaxIter && it - best_it < kStallIters) flag = 0;
         else if (res_p_best > 1e3 * c.tol) flag = -2;
         else if (res_d_best > 1e3 * c.tol) flag = -3;
         else flag = 0;

@@ -437,10 +437,19 @@ int cmpc_lpv_rounds_destroy(cmpc_lpv_rounds* h);
  *
  * HOST pointers, batch-major (problem p's block contiguous).  H n x n (its symmetric
  * part is used), A m_ineq x n, Aeq m_eq x n, row-major unless col_major (MATLAB
- * layout).  A/b, Aeq/beq, lb, ub may be NULL (absent); +-inf bounds are inactive;
- * all-zero constraint rows are dropped (or make the problem infeasible).
+ * layout).  A/b, Aeq/beq, lb, ub may be NULL (absent); b_r, ub_i = +inf and
+ * lb_i = -inf are inactive (their multipliers are exactly 0); b_r, ub_i = -inf,
+ * lb_i = +inf or a NaN bound make the problem infeasible; all-zero constraint rows
+ * are dropped (or make the problem infeasible).  A fixed variable lb_i == ub_i keeps
+ * both bound rows active: both of its bound multipliers come back positive, and
+ * only lambda_upper - lambda_lower, its equality multiplier, is determined.
  * exitflag: CMPC_QP_CONVERGED 1, CMPC_QP_MAXITER 0, CMPC_QP_INFEASIBLE -2,
- * CMPC_QP_UNBOUNDED -3, CMPC_QP_NONCONVEX -6 (quadprog's codes).
+ * CMPC_QP_UNBOUNDED -3, CMPC_QP_NONCONVEX -6 (quadprog's codes).  A solve that
+ * ends short of opts->tol returns its best iterate (x and the multipliers of that
+ * same iterate, residual its merit): 1 when that merit is below 1e3 tol; 0 when
+ * opts->max_iter cut it off while the merit was still improving (a new best within
+ * the last 3 iterations, so always for max_iter <= 3); otherwise -2 when the
+ * primal residual, else -3 when the dual residual, is what stayed above 1e3 tol.
  * ---------------------------------------------------------------------- */
 #define CMPC_QP_CONVERGED 1
 #define CMPC_QP_MAXITER 0

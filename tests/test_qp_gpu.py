@@ -172,3 +172,29 @@ def test_mex_gateway_column_major_batch(gpu_ctx):
     lam = out[4]
     assert np.abs(MH.values(MH.field(lam, "eqlin")).reshape(3, 3) - ref["lambda"]["eqlin"]).max() < 1e-6
     assert (MH.values(MH.field(out[3], "iterations")) > 0).all()
+
+
+def test_mex_gateway_returns_all_lambda_fields(gpu_ctx):
+    """lambda.ineqlin / eqlin / lower / upper of the gateway (m x B column-major each) against the
+    Python call, on problems whose general rows and both kinds of bound are active."""
+    import cmpc
+    import mex_harness as MH
+
+    rng = np.random.default_rng(11)
+    probs = []
+    for _ in range(2):
+        H, f, A, b, Aeq, beq, lb, ub = _rand_qp(rng, 12, 9, 3)
+        probs.append((H, 3.0 * f, A, b, Aeq, beq, np.maximum(lb, -0.6), np.minimum(ub, 0.6)))
+    H, f, A, b, Aeq, beq, lb, ub = probs[1]
+    probs.append((H, -f, -A, b, -Aeq, beq, -ub, -lb))   # its mirror image x -> -x: upper becomes lower
+    args = [np.stack([p[i] for p in probs]) for i in range(8)]
+    page = lambda a: np.moveaxis(a, 0, -1)
+    out, err = MH.call(tuple(page(a) for a in args), opts={"MaxIterations": 80.0, "OptimalityTolerance": 1e-9})
+    assert err is None, err
+    assert (MH.values(out[2]) == 1).all()
+    ref = cmpc.quadprog(*args, ctx=gpu_ctx)
+    assert (ref["exitflag"] == 1).all()
+    for key, rows in (("ineqlin", 9), ("eqlin", 3), ("lower", 12), ("upper", 12)):
+        got = MH.values(MH.field(out[4], key)).reshape(3, rows)
+        assert np.abs(ref["lambda"][key]).max() > 1e-2, key   # not a comparison of zeros
+        assert np.abs(got - ref["lambda"][key]).max() < 1e-6, key
