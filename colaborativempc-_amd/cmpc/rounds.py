@@ -9,6 +9,7 @@ Each round, on the GPU and on one stream:
   2. solve   — batched condensed IPM, one wavefront per agent  (cmpc_solve_mpc_batch_dev)
   3. advance — x0 <- x_1, u_prev <- u_0, local trajectory <- predicted positions
                (LPV_HP_N_main.py:106-117)                (cmpc_di_advance_dev)
+     (fused: 1-3 are one launch, cmpc_di_round_dev)
   4. exchange — all-gather of the (N+1) x 2 fp64 predicted positions of every
                agent over RCCL (torch.distributed "nccl" backend) — the
                replacement of the ROS topic exchange / np.swapaxes at :117.
@@ -60,7 +61,8 @@ class DIRounds:
 
         self.torch = torch
         self.scen, self.rank, self.world, self.group, self.comm = scen, rank, world, group, comm
-        # step(): rows built inside the solver launch (cmpc_di_solve_dev) instead of build() + solve()
+        # step(): rows built, and the round advanced, inside the solver launch (cmpc_di_round_dev) instead
+        # of build() + solve() + advance()
         self.fused = fused
         if scen.n_agents % world:
             raise ValueError("n_agents must be divisible by the number of ranks")
@@ -160,6 +162,18 @@ class DIRounds:
                                              ct.byref(self.opts), self._stream()))
         self._order_out()
 
+    def round(self):
+        """build_solve() + advance() as one call (cmpc_di_round_dev): where the v3 kernel covers the
+        problem the solver's launch also writes x0 <- x_1, u_prev <- u_0 and traj_local (the same
+        values advance() reads back from z), one launch less per round."""
+        lib = self.ctx.lib
+        self._order_in()
+        self.ctx.check(lib.cmpc_di_round_dev(self.ctx.h, ct.byref(self.dprm), ct.byref(self.ddims), _tptr(self.nbr),
+                                             _tptr(self.lane), _tptr(self.traj_all), ct.byref(self.mdims),
+                                             ct.byref(self.w), ct.byref(self.data), ct.byref(self.out),
+                                             ct.byref(self.opts), _tptr(self.traj_local), self._stream()))
+        self._order_out()
+
     def advance(self):
         self.ctx.check(self.ctx.lib.cmpc_di_advance_dev(self.ctx.h, ct.byref(self.dprm), ct.byref(self.ddims),
                                                         _tptr(self.z), _tptr(self.x0), _tptr(self.u_prev),
@@ -176,12 +190,13 @@ class DIRounds:
         if timer is not None:
             timer[0].record()
         if self.fused:
-            self.build_solve()
+            self.round()
         else:
             self.solve()
         if timer is not None:
             timer[1].record()
-        self.advance()
+        if not self.fused:
+            self.advance()
         self.exchange()
 
     def snapshot(self):

@@ -465,13 +465,15 @@ int cmpc_di_build_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_di
     return CMPC_OK;
 }
 
-int cmpc_di_solve_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* dd, const int* nbr,
-                      const double* lane, const double* traj_all, const cmpc_mpc_dims* dims,
-                      const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
-                      const cmpc_opts* opts, void* stream) {
-    if (!ctx) return CMPC_ERR_ARG;
+// cmpc_di_solve_dev, and with `traj_local` cmpc_di_round_dev: the advance too, from the fused launch's epilogue
+// where a v3 instantiation covers the problem, by the advance kernel after the solve elsewhere
+static int di_solve(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* dd, const int* nbr,
+                    const double* lane, const double* traj_all, const cmpc_mpc_dims* dims,
+                    const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
+                    const cmpc_opts* opts, double* traj_local, void* stream) {
     if (!lane || !traj_all || !dims || !in || !out || !out->z || (dd && dd->nb > 0 && !nbr))
         return fail(ctx, CMPC_ERR_ARG, "null argument");
+    if (traj_local && (!in->x0 || !in->u_prev)) return fail(ctx, CMPC_ERR_ARG, "null argument");
     cmpc::DiConst dc;
     int rc = di_const(ctx, prm, dd, &dc);
     if (rc != CMPC_OK) return rc;
@@ -489,6 +491,11 @@ int cmpc_di_solve_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_di
         cmpc::MpcPtrs p{in->A, in->B, in->x0, in->u_prev, nullptr, nullptr, nullptr, out->z, out->kkt, out->iters,
                         out->status, opts ? (unsigned long long*)opts->stamps : nullptr, nullptr};
         p.fuse = cmpc::DiFuse{nbr, lane, traj_all, dc, 1};
+        if (traj_local) {
+            p.fuse.adv_x0 = const_cast<double*>(in->x0);
+            p.fuse.adv_up = const_cast<double*>(in->u_prev);
+            p.fuse.adv_traj = traj_local;
+        }
         hipError_t e = hipSuccess;
         if (cmpc::mpc3_try_launch(c, p, dims->batch, s, &e)) {
             HIP_TRY(e);
@@ -500,7 +507,28 @@ int cmpc_di_solve_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_di
     cmpc::DiPtrs dp{nbr, lane, traj_all, const_cast<double*>(in->qlin), const_cast<double*>(in->C),
                     const_cast<double*>(in->h)};
     HIP_TRY(cmpc::di_build_launch(dc, dp, dd->batch, s));
-    return cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream);
+    rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream);
+    if (rc != CMPC_OK || !traj_local) return rc;
+    HIP_TRY(cmpc::di_advance_launch(dc, out->z, const_cast<double*>(in->x0), const_cast<double*>(in->u_prev),
+                                    traj_local, dd->batch, s));
+    return CMPC_OK;
+}
+
+int cmpc_di_solve_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* dd, const int* nbr,
+                      const double* lane, const double* traj_all, const cmpc_mpc_dims* dims,
+                      const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
+                      const cmpc_opts* opts, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    return di_solve(ctx, prm, dd, nbr, lane, traj_all, dims, w, in, out, opts, nullptr, stream);
+}
+
+int cmpc_di_round_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* dd, const int* nbr,
+                      const double* lane, const double* traj_all, const cmpc_mpc_dims* dims,
+                      const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
+                      const cmpc_opts* opts, double* traj_local, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!traj_local) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    return di_solve(ctx, prm, dd, nbr, lane, traj_all, dims, w, in, out, opts, traj_local, stream);
 }
 
 int cmpc_di_advance_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* d, const double* z,

@@ -67,6 +67,11 @@ struct DiFuse {
     const double* traj_all;
     DiConst c;
     int on;
+    // optional (cmpc_di_round_dev): the round's advance from the solver's epilogue.  All three or none:
+    // x0 and u_prev (the agent's own, overwritten with x_1 and u_0) and this rank's exchange rows
+    double* adv_x0 = nullptr;
+    double* adv_up = nullptr;
+    double* adv_traj = nullptr;
 };
 
 struct MpcPtrs {

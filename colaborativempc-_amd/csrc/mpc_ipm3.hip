@@ -922,14 +922,17 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         }
 #pragma unroll
         for (int r = 0; r < RX; ++r) {
+            // branch-free (as below, in every loop over the lane's rows): the row's values are formed on
+            // every lane and a lane without the row keeps what it had, by selects.  Under `if (ACT(r))`
+            // each row was an EXEC-masked region of its own, and the rows' chains ran one after another
             const double rvr = rowval(r, X, U, true), wr = wv(r);
-            if (ACT(r)) {
-                rp[r] = rvr + t[r] - wr;
-                nrp_l = nmax(nrp_l, fabs(rp[r]));
-                mu_l += t[r] * lam[r];
-            } else {
-                rp[r] = 0.0;
-            }
+            const bool ar = ACT(r);
+            const double rpv = rvr + t[r] - wr;
+            const double nrv = nmax(nrp_l, fabs(rpv));
+            const double muv = mu_l + t[r] * lam[r];
+            rp[r] = ar ? rpv : 0.0;
+            nrp_l = ar ? nrv : nrp_l;
+            mu_l = ar ? muv : mu_l;
         }
         const double mu = wave_sum(mu_l) / mact;
         const double res = nmax(nmax(wave_max(nrd_l) / wave_max(gs_l), wave_max(nrs_l) / c.qs_max),
@@ -997,7 +1000,12 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         double tin[RX];
         auto theta = [&](double oz) __attribute__((always_inline)) {
 #pragma unroll
-            for (int r = 0; r < RX; ++r) tin[r] = ACT(r) ? 1.0 / (t[r] + oz) : 0.0;
+            for (int r = 0; r < RX; ++r) {
+                // the division outside the select: inside it, each row's became a masked region and the
+                // divisions' chains ran one after another (t_r = 1 on a lane without the row)
+                const double ti = 1.0 / (t[r] + oz);
+                tin[r] = ACT(r) ? ti : 0.0;
+            }
 #pragma unroll
             for (int r = 0; r < RX; ++r) th[r] = lam[r] * tin[r];
 #pragma unroll
@@ -1531,10 +1539,6 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             // pass 1: Mehrotra's second-order term dt_aff * dl_aff from the predictor still in (rho, gdu, dsg)
 #pragma unroll
             for (int r = 0; r < RX; ++r) {
-                if (!ACT(r)) {
-                    rho[r] = 0.0;
-                    continue;
-                }
                 double rc = -t[r] * lam[r];
                 if (pass) {
                     const double sd = (lo && slk(r) >= 0) ? sgn(r) * dsg[slk(r)] : 0.0;
@@ -1542,7 +1546,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     const double dla = rho[r] + th[r] * (gdu[r] + sd);
                     rc += sig_c * mu - dta * dla;
                 }
-                rho[r] = (rc + lam[r] * rp[r]) * tin[r];
+                const double rv = (rc + lam[r] * rp[r]) * tin[r];
+                rho[r] = ACT(r) ? rv : 0.0;
             }
             // rho~ (stable slack-group form) of the stage rows enters only through C' rho~
             if (lo && own) {
@@ -1651,6 +1656,10 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             double Lr[16];
 #pragma unroll
             for (int cc = 0; cc < 16; ++cc) Lr[cc] = Lme[(l & 15) * 17 + cc];
+            // y_J / x_J are row group J's to store; the other groups store to a sink instead of under an
+            // EXEC mask: their own slot of dU, which is dead from the last rowval(dX, dU) until it is
+            // rewritten below (an index relative to vb)
+            const int sink = (int)(dU - vb) + ((l >> 4) < T ? l : (l & 15));
 #pragma unroll
             for (int J = 0; J < T; ++J) {
                 double pr4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1669,8 +1678,9 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     }
                     wsync();
                 }
-                double rv = 0.0;
-                if ((l >> 4) == J) rv = vb[J * 16 + (l & 15)] - (J > 0 ? red[l & 15] : 0.0);
+                // (unconditional reads; the other row groups' residual is the 0 it was)
+                const double vJ = vb[J * 16 + (l & 15)], rJ = J > 0 ? red[l & 15] : 0.0;
+                double rv = ((l >> 4) == J) ? vJ - rJ : 0.0;
                 {  // y_J = L_JJ^{-1} r_J: row J broadcasts its lanes, four independent fma chains
                     double y4[4] = {0.0, 0.0, 0.0, 0.0};
                     const double rs = dpp_settled(rv);
@@ -1680,7 +1690,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     });
                     rv = (y4[0] + y4[1]) + (y4[2] + y4[3]);
                 }
-                if ((l >> 4) == J) vb[J * 16 + (l & 15)] = rv;
+                vb[(l >> 4) == J ? J * 16 + (l & 15) : sink] = rv;
                 wsync();
             }
             // ---- backward solve L' x = y ----
@@ -1696,7 +1706,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     for (int r = 0; r < 4; ++r)
                         p = fma(acc[I * (I + 1) / 2 + J][r], vb[I * 16 + (l >> 4) + 4 * r], p);
                 if (J + 1 < T) p = sum_groups(p);
-                double rv = ((l >> 4) == J) ? vb[J * 16 + (l & 15)] - p : 0.0;
+                const double vJ = vb[J * 16 + (l & 15)];
+                double rv = ((l >> 4) == J) ? vJ - p : 0.0;
                 {  // x_J = L_JJ^{-T} r_J
                     double x4[4] = {0.0, 0.0, 0.0, 0.0};
                     const double rs = dpp_settled(rv);
@@ -1706,10 +1717,13 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     });
                     rv = (x4[0] + x4[1]) + (x4[2] + x4[3]);
                 }
-                if ((l >> 4) == J) vb[J * 16 + (l & 15)] = rv;
+                vb[(l >> 4) == J ? J * 16 + (l & 15) : sink] = rv;
                 wsync();
             }
-            for (int i = l; i < NP; i += 64) dU[i] = (i < n) ? vb[i] : 0.0;
+            for (int i = l; i < NP; i += 64) {
+                const double v = vb[i];
+                dU[i] = (i < n) ? v : 0.0;
+            }
             }
             if constexpr (W2) {  // each pass's dU to wave 1 (one slot per pass)
                 double* xu = sm + (pass ? L.xu1 : L.xu0);
@@ -1742,13 +1756,15 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             double amax_l = 1.0e300;
 #pragma unroll
             for (int r = 0; r < RX; ++r) {
-                if (!ACT(r)) continue;
+                const bool ar = ACT(r);
                 const double sd = sdr(r);
                 const double dtv = -rp[r] - gdu[r] - sd;
                 const double dlv = rho[r] + th[r] * (gdu[r] + sd);
                 // ratio tests by the hardware reciprocal: the step is cut to 0.995 of it anyway
-                if (dtv < 0.0) amax_l = fmin(amax_l, -t[r] * __builtin_amdgcn_rcp(dtv));
-                if (dlv < 0.0) amax_l = fmin(amax_l, -lam[r] * __builtin_amdgcn_rcp(dlv));
+                const double at = fmin(amax_l, -t[r] * __builtin_amdgcn_rcp(dtv));
+                amax_l = (ar && dtv < 0.0) ? at : amax_l;
+                const double al = fmin(amax_l, -lam[r] * __builtin_amdgcn_rcp(dlv));
+                amax_l = (ar && dlv < 0.0) ? al : amax_l;
             }
             const double amax = wave_min(amax_l);
             if (!pass) {
@@ -1756,9 +1772,10 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 double mua_l = 0.0;
 #pragma unroll
                 for (int r = 0; r < RX; ++r) {
-                    if (!ACT(r)) continue;
                     const double sd = sdr(r);
-                    mua_l += (t[r] + a * (-rp[r] - gdu[r] - sd)) * (lam[r] + a * (rho[r] + th[r] * (gdu[r] + sd)));
+                    const double mv =
+                        mua_l + (t[r] + a * (-rp[r] - gdu[r] - sd)) * (lam[r] + a * (rho[r] + th[r] * (gdu[r] + sd)));
+                    mua_l = ACT(r) ? mv : mua_l;
                 }
                 const double mu_aff = wave_sum(mua_l) / mact;
                 const double ratio = mu > 0.0 ? mu_aff / mu : 0.0;
@@ -1771,24 +1788,27 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 for (int bt = 0; bt < kMaxBacktrack; ++bt) {
                     double mn_l = 0.0, pm_l = INFINITY;
 #pragma unroll
-                    for (int r = 0; r < RX; ++r)
-                        if (ACT(r)) {
-                            const double sd = sdr(r);
-                            const double pr = (t[r] + alpha * (-rp[r] - gdu[r] - sd)) *
-                                              (lam[r] + alpha * (rho[r] + th[r] * (gdu[r] + sd)));
-                            mn_l += pr;
-                            pm_l = fmin(pm_l, pr);
-                        }
+                    for (int r = 0; r < RX; ++r) {
+                        const bool ar = ACT(r);
+                        const double sd = sdr(r);
+                        const double pr = (t[r] + alpha * (-rp[r] - gdu[r] - sd)) *
+                                          (lam[r] + alpha * (rho[r] + th[r] * (gdu[r] + sd)));
+                        const double ms = mn_l + pr, pm = fmin(pm_l, pr);
+                        mn_l = ar ? ms : mn_l;
+                        pm_l = ar ? pm : pm_l;
+                    }
                     if (wave_min(pm_l) >= kNbhdGamma * (wave_sum(mn_l) / mact)) break;
                     alpha *= 0.8;
                 }
 #pragma unroll
-                for (int r = 0; r < RX; ++r)
-                    if (ACT(r)) {
-                        const double sd = sdr(r);
-                        t[r] = fma(alpha, -rp[r] - gdu[r] - sd, t[r]);
-                        lam[r] = fma(alpha, rho[r] + th[r] * (gdu[r] + sd), lam[r]);
-                    }
+                for (int r = 0; r < RX; ++r) {
+                    const bool ar = ACT(r);
+                    const double sd = sdr(r);
+                    const double tn = fma(alpha, -rp[r] - gdu[r] - sd, t[r]);
+                    const double ln = fma(alpha, rho[r] + th[r] * (gdu[r] + sd), lam[r]);
+                    t[r] = ar ? tn : t[r];
+                    lam[r] = ar ? ln : lam[r];
+                }
 #pragma unroll
                 for (int j = 0; j < NS; ++j) sg[j] = fma(alpha, dsg[j], sg[j]);
                 STAMP(12);
@@ -1852,6 +1872,19 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         const int kk = i / NU, j = i - kk * NU;
         z[(size_t)(N + 1) * NXE + i] = U[i];
         z[(size_t)(N + 1) * NXE + n + i] = U[i] - (kk ? U[(kk - 1) * NU + j] : sup[j]);
+    }
+    if (P.fuse.on && P.fuse.adv_traj) {
+        // the round's advance (cmpc_di_round_dev), from the X and U this epilogue holds: x0 <- x_1, u_prev <- u_0,
+        // the agent's exchanged positions <- predicted (p_x, p_y): what di_advance_kernel reads back from z.
+        // x0 / u_prev are this agent's own (read while staging); traj_all is read by workgroups that start
+        // later in the same launch and is never written here (the exchange stays a step of its own)
+        double* tl = P.fuse.adv_traj + (size_t)b * (N + 1) * 2;
+        for (int kk = l; kk <= N; kk += 64) {
+            tl[kk * 2 + 0] = X[kk * NX + 0];
+            tl[kk * 2 + 1] = X[kk * NX + 1];
+        }
+        if (l < NX) P.fuse.adv_x0[(size_t)b * NX + l] = X[NX + l];
+        if (l < NU) P.fuse.adv_up[(size_t)b * NU + l] = U[l];
     }
     if (l == 0) {
         if (P.kkt) P.kkt[b] = kkt;

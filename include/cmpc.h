@@ -332,6 +332,17 @@ int cmpc_di_solve_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_di
                       const double* lane, const double* traj_all, const cmpc_mpc_dims* dims,
                       const cmpc_mpc_weights* w, const cmpc_mpc_data* data, const cmpc_mpc_out* out,
                       const cmpc_opts* opts, void* hip_stream);
+/* cmpc_di_solve_dev followed by cmpc_di_advance_dev(z = out->z, x0 = data->x0, u_prev = data->u_prev,
+ * traj_local), with the same results: where the v3 kernel covers the problem the solver's launch writes
+ * x0 <- x_1, u_prev <- u_0 (data->x0 / u_prev: written despite the const) and traj_local from the
+ * trajectory it holds, one launch for the round's build, solve and advance; otherwise the advance kernel
+ * follows the solve.  traj_all is only read (workgroups that start later in the launch still build their
+ * rows from it: the Jacobi round); the exchange traj_local -> traj_all stays the caller's next step, and
+ * traj_local must not alias traj_all. */
+int cmpc_di_round_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* ddims, const int* nbr,
+                      const double* lane, const double* traj_all, const cmpc_mpc_dims* dims,
+                      const cmpc_mpc_weights* w, const cmpc_mpc_data* data, const cmpc_mpc_out* out,
+                      const cmpc_opts* opts, double* traj_local /* batch x (N+1) x 2 */, void* hip_stream);
 int cmpc_di_advance_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims* dims,
                         const double* z /* batch x nz */, double* x0 /* batch x nx */,
                         double* u_prev /* batch x nu */, double* traj_local /* batch x (N+1) x 2 */,

@@ -329,6 +329,41 @@ __global__ __launch_bounds__(64,1) void k_dpp_tp(const double* gA, double* out, 
   if (l == 0) cyc[blockIdx.x] = (t1 - t0);
   out[blockIdx.x * 64 + l] = s;
 }
+// One conditional LDS store per link of a dependent fma chain of 32 (the v3 iteration's short masked regions:
+// `if (lane predicate) lds[i] = v`).  MODE 0: the store under the predicate (EXEC-masked: saveexec, the
+// execz branch, store, restore); MODE 1: every lane stores, a masked lane to a sink slot picked by a select
+// on the address.  `thr` (lanes below it store) comes from memory, so the predicate is a run-time one; 16:
+// some lanes active (execz falls through), 0: none (execz taken).  MODE 2: the chain alone.
+template <int MODE>
+__global__ __launch_bounds__(64,1) void k_mask_store(const double* gA, const int* gthr, double* out, unsigned long long* cyc) {
+  __shared__ double buf[128];
+  int l = threadIdx.x;
+  buf[l] = 0.0; buf[64 + l] = 0.0;
+  double v = gA[l], a = gA[64 + l] * 1e-3;
+  int thr = gthr[0];
+  __syncthreads();
+  unsigned long long t0 = stamp();
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    v = fma(v, a, 0.5);
+    asm volatile("" : "+v"(thr));  // opaque per link: the regions are neither merged nor hoisted
+    const bool on = l < thr;
+    if constexpr (MODE == 0) {
+      if (on) buf[l] = v;
+    } else if constexpr (MODE == 1) {
+      buf[on ? l : 64 + l] = v;
+    } else if constexpr (MODE == 3) {  // a body with an LDS read: the compiler keeps the execz branch
+      if (on) buf[l] = v + buf[64 + l];
+    } else if constexpr (MODE == 4) {  // the same, read and store unconditional, sink address
+      buf[on ? l : 64 + l] = v + buf[64 + l];
+    }
+    wsync();
+  }
+  asm volatile("v_mov_b64 %0, %0" : "+v"(v));
+  unsigned long long t1 = stamp();
+  if (l == 0) cyc[blockIdx.x] = (t1 - t0);
+  out[blockIdx.x * 64 + l] = v + buf[l] + buf[64 + l];
+}
 int main() {
   const int nb = 1024;
   std::vector<double> hA(N*NX*NX*1 + 4096), hK(256);
@@ -338,6 +373,8 @@ int main() {
   hipMalloc(&dA, hA.size() * 8); hipMalloc(&dK, 256 * 8); hipMalloc(&out, nb * 64 * 8); hipMalloc(&cyc, 2048 * 8);
   hipMemcpy(dA, hA.data(), hA.size() * 8, hipMemcpyHostToDevice); hipMemcpy(dK, hK.data(), 256 * 8, hipMemcpyHostToDevice);
   std::vector<unsigned long long> hc(2048);
+  int* dthr; hipMalloc(&dthr, sizeof(int));
+  const int thr_of[2] = {16, 0};
   auto rep = [&](const char* nm, int div) {
     hipDeviceSynchronize(); hipMemcpy(hc.data(), cyc, 2048 * 8, hipMemcpyDeviceToHost);
     double s = 0; for (int i = 0; i < nb; ++i) s += hc[i];
@@ -362,6 +399,19 @@ int main() {
     hipLaunchKernelGGL(k_readlane, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("readlane_d->fma dep", 32);
     hipLaunchKernelGGL(k_div, dim3(nb), dim3(64), 0, 0, dA, out, cyc); rep("f64 div dep", 16);
     { double s = 0; for (int i = 0; i < nb; ++i) s += hc[1024 + i]; printf("%-28s %10.1f cyc per unit\n", "f64 sqrt dep", s / nb / 16); }
+    for (int taken = 0; taken < 2; ++taken) {  // thr 16: some lanes store (execz not taken); 0: none (taken)
+      hipMemcpy(dthr, &thr_of[taken], sizeof(int), hipMemcpyHostToDevice);
+      hipLaunchKernelGGL(k_mask_store<2>, dim3(nb), dim3(64), 0, 0, dA, dthr, out, cyc);
+      rep("fma chain alone (per link)", 32);
+      hipLaunchKernelGGL(k_mask_store<0>, dim3(nb), dim3(64), 0, 0, dA, dthr, out, cyc);
+      rep(taken ? "fma + EXEC-masked lds store, execz taken" : "fma + EXEC-masked lds store, execz not taken", 32);
+      hipLaunchKernelGGL(k_mask_store<1>, dim3(nb), dim3(64), 0, 0, dA, dthr, out, cyc);
+      rep(taken ? "fma + sink-address lds store, no lane real" : "fma + sink-address lds store, 16 lanes real", 32);
+      hipLaunchKernelGGL(k_mask_store<3>, dim3(nb), dim3(64), 0, 0, dA, dthr, out, cyc);
+      rep(taken ? "fma + EXEC-masked lds read+store, execz taken" : "fma + EXEC-masked lds read+store, execz not taken", 32);
+      hipLaunchKernelGGL(k_mask_store<4>, dim3(nb), dim3(64), 0, 0, dA, dthr, out, cyc);
+      rep(taken ? "fma + sink-address lds read+store, no lane real" : "fma + sink-address lds read+store, 16 lanes real", 32);
+    }
   }
   return 0;
 }
