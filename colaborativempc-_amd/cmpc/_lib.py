@@ -114,8 +114,13 @@ class cmpc_di_dims(ct.Structure):
     _fields_ = [(k, ct.c_int) for k in ("batch", "N", "nb", "self_offset")]
 
 
+class cmpc_nbr_dims(ct.Structure):
+    _fields_ = [(k, ct.c_int) for k in ("batch", "N", "nb", "self_offset", "n_total", "k0", "k1")]
+
+
 CMPC_ROUNDS_HOST_EXCHANGE = 1
 CMPC_ROUNDS_NO_HALT = 2
+CMPC_ROUNDS_RESELECT = 4   # every round starts with the (0, 0) neighbour selection on the exchange buffer
 
 
 class cmpc_lpv_rounds_dims(ct.Structure):
@@ -190,6 +195,7 @@ SIGNATURES = {
                                      ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out), ct.POINTER(cmpc_opts),
                                      _DP, ct.c_void_p]),
     "cmpc_lpv_gather_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_di_dims), _IP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_nbr_select_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_nbr_dims), _DP, _IP, _DP, ct.c_void_p]),
     "cmpc_lpv_advance_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_di_dims), _DP, _DP, _DP, _DP, _DP, _DP,
                                         _IP, _IP, ct.c_void_p]),
     "cmpc_di_advance_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_di_params), ct.POINTER(cmpc_di_dims),

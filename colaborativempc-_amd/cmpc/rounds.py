@@ -4,6 +4,9 @@ variant ROS/src/planner_experiments/src/LPV_ROS_main.py:124-150, re-designed as
 one process per GPU).
 
 Each round, on the GPU and on one stream:
+  0. select  — optional (`reselect=r`, every r rounds): each local agent's nb nearest
+               other agents from the exchanged trajectories, into the neighbour
+               table in place                              (cmpc_nbr_select_dev)
   1. build   — every local agent's stage rows / linear cost from the previous
                round's exchanged trajectories            (cmpc_di_build_dev)
   2. solve   — batched condensed IPM, one wavefront per agent  (cmpc_solve_mpc_batch_dev)
@@ -54,9 +57,51 @@ def exchange_positions(traj_all, traj_local, world=1, group=None, comm=None):
     dist.all_gather_into_tensor(traj_all, traj_local.contiguous(), group=group)
 
 
+def select_neighbours_dev(traj_all, nb, batch=None, self_offset=0, window=(0, 0), out=None, dist2=None, ctx=None,
+                          stream=None):
+    """The ``nb`` nearest other agents of the local agents [self_offset, self_offset + batch) (default: all)
+    out of the exchange buffer ``traj_all`` (n_total, N+1, 2), a contiguous fp64 CUDA tensor — one launch of
+    cmpc_nbr_select_dev on ``stream`` (default: torch's current one), no host synchronisation.  The rule is
+    ``scenarios.select_neighbours``'s (score = min over the stages of ``window`` of the squared distance, ties
+    by index, the agent itself left out by index), the result bit-equal to it.  Writes the (batch, nb) int32
+    global indices, nearest first, into ``out`` (allocated when None) and returns it; ``dist2`` (batch, nb)
+    fp64, optional, receives their scores.  Nearest first is not the reference's index order of ns[i]: it
+    only reorders an agent's collision rows and the columns of ``planes``."""
+    import torch
+
+    if traj_all.dim() != 3 or traj_all.shape[2] != 2 or traj_all.dtype != torch.float64 or not traj_all.is_cuda or \
+            not traj_all.is_contiguous():
+        raise ValueError("traj_all: a contiguous (n_total, N+1, 2) float64 CUDA tensor")
+    n_total, N = int(traj_all.shape[0]), int(traj_all.shape[1]) - 1
+    batch = n_total - self_offset if batch is None else int(batch)
+    if out is None:
+        out = torch.empty((max(batch, 0), max(int(nb), 0)), dtype=torch.int32, device=traj_all.device)
+    for name, t, dt in (("out", out, torch.int32), ("dist2", dist2, torch.float64)):
+        if t is not None and (t.device != traj_all.device or t.dtype != dt or tuple(t.shape) != (batch, nb) or
+                              not t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous ({batch}, {nb}) {dt} tensor on {traj_all.device}")
+    ctx = ctx or L.default_context(traj_all.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(traj_all.device)
+    dims = L.cmpc_nbr_dims(batch, N, int(nb), int(self_offset), n_total, int(window[0]), int(window[1]))
+    ctx.check(ctx.lib.cmpc_nbr_select_dev(ctx.h, ct.byref(dims), _tptr(traj_all), _tptr(out),
+                                          None if dist2 is None else _tptr(dist2),
+                                          ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+    return out
+
+
 class DIRounds:
+    """Device-resident consensus rounds of the synthetic double-integrator agents (module docstring).
+
+    ``reselect`` = r > 0: the neighbour table ``self.nbr`` is re-selected on the device, in place, at the
+    start of ``step()`` on rounds 0, r, 2r, ... (``select_neighbours_dev`` with ``reselect_window``, on the
+    round's stream, before the rows are built), so the collision rows and the coverage term follow the agents
+    that are nearest now instead of those of the scenario's t = 0 table.  0 (the default): the table stays
+    what the scenario gave, and ``step()`` is launch for launch what it was.  Selected neighbours come nearest
+    first, not in the reference's index order of ns[i]; only the order of an agent's collision rows follows."""
+
     def __init__(self, scen, rank=0, world=1, device=None, ctx=None, tol=None, max_iter=None, group=None,
-                 fp32=False, comm=None, fused=True, lpt=None):
+                 fp32=False, comm=None, fused=True, lpt=None, reselect=0, reselect_window=(0, 0)):
         import torch
 
         self.torch = torch
@@ -64,6 +109,7 @@ class DIRounds:
         # step(): rows built, and the round advanced, inside the solver launch (cmpc_di_round_dev) instead
         # of build() + solve() + advance()
         self.fused = fused
+        self.reselect, self.reselect_window, self.rounds_done = int(reselect), tuple(reselect_window), 0
         if scen.n_agents % world:
             raise ValueError("n_agents must be divisible by the number of ranks")
         self.dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -182,9 +228,18 @@ class DIRounds:
     def exchange(self):
         exchange_positions(self.traj_all, self.traj_local, self.world, self.group, self.comm)
 
+    def select_neighbours(self, window=None):
+        """One selection into ``self.nbr``, in place: this rank's agents against the exchange buffer as it
+        stands (``select_neighbours_dev``; ``window`` defaults to ``reselect_window``)."""
+        select_neighbours_dev(self.traj_all, self.nb, self.B, self.off, self.reselect_window if window is None
+                              else window, out=self.nbr, ctx=self.ctx)
+
     def step(self, timer=None):
         """One consensus round.  `timer` (start, stop) events bracket the solve launch (with
         `fused`, the launch that builds and solves)."""
+        if self.reselect > 0 and self.nb and self.rounds_done % self.reselect == 0:
+            self.select_neighbours()
+        self.rounds_done += 1
         if not self.fused:
             self.build()
         if timer is not None:
@@ -220,13 +275,21 @@ class LPVRounds:
     round's Last_xPredicted), u_last (n, N, 2), nbr (n, nb) neighbour indices (the reference: all
     other agents, :82-85), u_old (n, 2) (default 0, PlannerLPV's initial OldSteering /
     OldAccelera), traj (n, N+1, 2) (default x_last[:, :, 7:9], the reference's initial
-    ``agents``)."""
+    ``agents``).
 
-    def __init__(self, bp, x0, x_last, u_last, nbr, u_old=None, traj=None, rank=0, world=1, group=None, comm=None):
+    ``reselect`` = r > 0 (with ``reselect_window``): ``nbr`` is only the table's first content — at the start
+    of ``step()`` on rounds 0, r, 2r, ... the table is re-selected on the device, in place
+    (``select_neighbours_dev``, before the gather, on the round's stream).  The default 0 keeps the table for
+    good, as the reference.  Selected neighbours come nearest first, not in the reference's index order of
+    ns[i]: the order of an agent's collision rows and of the ``planes`` columns follows."""
+
+    def __init__(self, bp, x0, x_last, u_last, nbr, u_old=None, traj=None, rank=0, world=1, group=None, comm=None,
+                 reselect=0, reselect_window=(0, 0)):
         import torch
 
         self.torch, self.bp, self.ctx = torch, bp, bp.ctx
         self.rank, self.world, self.group, self.comm = rank, world, group, comm
+        self.reselect, self.reselect_window, self.rounds_done = int(reselect), tuple(reselect_window), 0
         x0 = np.asarray(x0, np.float64)
         n, N = x0.shape[0], bp.N
         if n % world:
@@ -271,6 +334,12 @@ class LPVRounds:
     def _stream(self):
         return ct.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
+    def select_neighbours(self, window=None):
+        """One selection into ``self.nbr``, in place: this rank's agents against the exchange buffer as it
+        stands (``select_neighbours_dev``; ``window`` defaults to ``reselect_window``)."""
+        select_neighbours_dev(self.traj_all, self.nb, self.B, self.off, self.reselect_window if window is None
+                              else window, out=self.nbr, ctx=self.ctx)
+
     def gather(self):
         lib = self.ctx.lib
         self.ctx.check(lib.cmpc_lpv_gather_dev(self.ctx.h, ct.byref(self.rdims), _tptr(self.nbr), _tptr(self.traj_all),
@@ -313,6 +382,9 @@ class LPVRounds:
         ``halt``: like the reference (LPV_HP_N_main.py:102-111, "QUIT..."), raise InfeasibleRound when an
         agent of this rank is infeasible (reads a device counter: one host synchronisation per round;
         ``halt=False`` leaves the check to the caller, ``infeasible()``)."""
+        if self.reselect > 0 and self.nb and self.rounds_done % self.reselect == 0:
+            self.select_neighbours()
+        self.rounds_done += 1
         self.gather()
         if timer is not None:
             timer[0].record()
@@ -362,10 +434,12 @@ class InfeasibleRound(RuntimeError):
 class LPVRoundsHandle:
     """The same rounds through the C ABI's round handle (cmpc_lpv_rounds_*): the library owns the
     device state; no torch.  What a MATLAB (MEX) or C host drives.  Arguments as LPVRounds;
-    ``host_exchange``: the caller exchanges positions between steps (get_traj / set_traj)."""
+    ``host_exchange``: the caller exchanges positions between steps (get_traj / set_traj).  ``reselect``:
+    CMPC_ROUNDS_RESELECT — every round starts with the (0, 0) neighbour selection on the handle's exchange
+    buffer (``nbr`` is only the table's first content), as ``LPVRounds(reselect=1)``."""
 
     def __init__(self, bp, x0, x_last, u_last, nbr, u_old=None, traj=None, rank=0, world=1, host_exchange=False,
-                 halt=True):
+                 halt=True, reselect=False):
         self.bp, self.ctx = bp, bp.ctx
         x0 = L.f64(x0)
         n, N = x0.shape[0], bp.N
@@ -375,7 +449,8 @@ class LPVRoundsHandle:
         B = n // world
         sl = slice(rank * B, (rank + 1) * B)
         self.N, self.nb, self.B, self.n = N, nbr.shape[1], B, n
-        flags = (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (0 if halt else L.CMPC_ROUNDS_NO_HALT)
+        flags = (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (0 if halt else L.CMPC_ROUNDS_NO_HALT) | \
+            (L.CMPC_ROUNDS_RESELECT if reselect else 0)
         self.dims = L.cmpc_lpv_rounds_dims(n, B, rank * B, N, self.nb, flags)
         keep = [L.f64(x0[sl]), L.f64(np.asarray(x_last)[sl]), L.f64(np.asarray(u_last)[sl]),
                 None if u_old is None else L.f64(np.asarray(u_old)[sl]), L.i32(nbr[sl]),

@@ -12,7 +12,8 @@ coverage weight wq = 5.
 Agents sit on a straight 3-lane road: p_x = 0.5 floor(i/3) + U(-.05,.05),
 p_y = {-0.5, 0, 0.5}[i%3] + U(-.05,.05), v_x ~ U(1.0, 1.6), v_y = 0, drawn from
 numpy.random.default_rng(20240101) in that order.  Neighbours: the nb nearest
-agents by initial position (fixed graph).  Previous predictions: constant-velocity
+agents by initial position (a fixed graph unless the rounds re-select it: `select_neighbours`,
+`rounds.DIRounds(reselect=r)`).  Previous predictions: constant-velocity
 rollout, as initialise_agents does (utilities/misc.py:155-210).
 """
 from __future__ import annotations
@@ -91,6 +92,39 @@ def nearest_neighbours(pos, nb):
         row = [j for j in idx[i] if j != i][:nb]
         out[i] = row
     return out
+
+
+def select_neighbours(traj, nb, window=(0, 0), rows=None, return_dist2=False):
+    """Host statement of the device neighbour selection (cmpc_nbr_select_dev, include/cmpc.h): for every
+    agent g in ``rows`` (default: all) the ``nb`` nearest other agents of ``traj`` (n, N+1, 2).
+
+    score(g, j) = min over the stages k0..k1 of ``window`` of dx*dx + dy*dy (numpy's min: a NaN at any
+    stage of the window makes the score NaN); a NaN score counts as +inf; candidates are ordered by
+    (score, j) ascending and j = g is left out by index, never by distance.  Returns (len(rows), nb)
+    int32 global indices, nearest first (and their scores with ``return_dist2``).  Window (0, 0) is
+    "nearest now" — on distinct distances what ``nearest_neighbours`` gives for the stage-0 positions;
+    (0, N) is the closest predicted approach.  The reference's ns[i] (LPV_HP_N_main.py:82-85) is in
+    index order: nearest first only reorders an agent's collision rows and the columns of ``planes``."""
+    traj = np.asarray(traj, np.float64)
+    n, (k0, k1) = traj.shape[0], window
+    if not (0 <= k0 <= k1 < traj.shape[1]) or not (0 <= nb < n):
+        raise ValueError("need 0 <= k0 <= k1 <= N and 0 <= nb < n")
+    rows = np.arange(n) if rows is None else np.arange(n)[rows]
+    w = traj[:, k0:k1 + 1]
+    score = np.empty((len(rows), n))
+    step = max(1, (1 << 22) // (n * w.shape[1]))           # rows per block: bounds the (block, n, stages) arrays
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(0, len(rows), step):
+            r = rows[i:i + step]
+            dx = w[None, :, :, 0] - w[r, None, :, 0]
+            dy = w[None, :, :, 1] - w[r, None, :, 1]
+            score[i:i + step] = (dx * dx + dy * dy).min(axis=2)
+    score[np.isnan(score)] = np.inf
+    j = np.broadcast_to(np.arange(n), score.shape)
+    order = np.lexsort((j, score), axis=1)                 # by score, then by index
+    order = order[order != rows[:, None]].reshape(len(rows), n - 1)[:, :nb]
+    idx = order.astype(np.int32)
+    return (idx, np.take_along_axis(score, order, axis=1)) if return_dist2 else idx
 
 
 def make_di(n_agents, N, nb=2, dim=2, seed=SEED):

@@ -370,6 +370,24 @@ int cmpc_lpv_gather_dev(cmpc_ctx* ctx, const cmpc_di_dims* d, const int* nbr, co
     return CMPC_OK;
 }
 
+int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* traj_all, int* nbr, double* dist2,
+                        void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!d || !traj_all) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    if (d->batch < 0 || d->N < 1 || d->nb < 0 || d->nb > CMPC_MAX_MC - 4 || d->nb >= d->n_total)
+        return fail(ctx, CMPC_ERR_ARG, "bad selection dimensions (N >= 1, 0 <= nb <= 12, nb < n_total)");
+    if (d->self_offset < 0 || (long long)d->self_offset + d->batch > d->n_total)
+        return fail(ctx, CMPC_ERR_ARG, "local agents outside the population (self_offset + batch <= n_total)");
+    if (d->k0 < 0 || d->k0 > d->k1 || d->k1 > d->N) return fail(ctx, CMPC_ERR_ARG, "stage window outside 0 <= k0 <= k1 <= N");
+    if (d->batch == 0 || d->nb == 0) return CMPC_OK;
+    if (!nbr) return fail(ctx, CMPC_ERR_ARG, "null neighbour table");
+    int rc = set_device(ctx);
+    if (rc != CMPC_OK) return rc;
+    const cmpc::NbrConst c{d->batch, d->N, d->nb, d->self_offset, d->n_total, d->k0, d->k1};
+    HIP_TRY(cmpc::nbr_select_launch(c, traj_all, nbr, dist2, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
 int cmpc_lpv_advance_dev(cmpc_ctx* ctx, const cmpc_di_dims* d, const double* z, double* x0, double* x_last,
                          double* u_last, double* u_old, double* traj_local, const int* status, int* infeasible,
                          void* stream) {

@@ -250,6 +250,13 @@ hipError_t lpv_advance_launch(int N, const double* z, double* x0, double* x_last
                               double* traj_local, int batch, hipStream_t s, const int* status = nullptr,
                               int* infeasible = nullptr);
 
+// Neighbour selection (nbr_select.hip): the nb nearest other agents of every local agent by
+// (min over stages k0..k1 of the squared distance, index), nearest first; dist2 may be null
+struct NbrConst {
+    int batch, N, nb, self_offset, n_total, k0, k1;
+};
+hipError_t nbr_select_launch(const NbrConst& c, const double* traj_all, int* nbr, double* dist2, hipStream_t s);
+
 // Synthetic double-integrator family (bench workload).
 
 struct DiPtrs {

@@ -2,7 +2,7 @@
 // LPV_HP_N_main.py:96-117 for hosts that own no device memory (MATLAB through the MEX gateway, C).
 // The handle owns this rank's agent state and the node-global exchange buffer in one device
 // allocation; a round chains the C-ABI device entry points on the context's stream:
-//   cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
+//   [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's
 // communicator (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).
 #include <cstring>
@@ -42,7 +42,10 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
     if (d.N < 1 || d.nb < 0 || 4 + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
         d.self_offset + d.batch > d.n_total)
         return fail(ctx, CMPC_ERR_ARG, "bad rounds dimensions (1 <= batch, self_offset + batch <= n_total, nb <= 12)");
-    if (d.flags & ~(CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT)) return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
+    if (d.flags & ~(CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT))
+        return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
+    if ((d.flags & CMPC_ROUNDS_RESELECT) && d.nb >= d.n_total)
+        return fail(ctx, CMPC_ERR_ARG, "CMPC_ROUNDS_RESELECT selects nb < n_total neighbours");
     if (track->nseg < 1 || track->nseg > CMPC_MAX_SEG) return fail(ctx, CMPC_ERR_UNSUPPORTED, "track has 1..32 segments");
     if (!in->x0 || !in->x_last || !in->u_last || (d.nb > 0 && !in->nbr))
         return fail(ctx, CMPC_ERR_ARG, "null initial state");
@@ -135,8 +138,13 @@ int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* 
     hipStream_t s = ctx->stream;
     const cmpc_di_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset};
     const int nb = h->d.nb;
+    const cmpc_nbr_dims sd{h->d.batch, h->d.N, nb, h->d.self_offset, h->d.n_total, 0, 0};
     int done = 0, bad = 0, rc;
     for (int r = 0; r < rounds; ++r) {
+        // CMPC_ROUNDS_RESELECT: this round's neighbours are the nb nearest in the exchange buffer as it stands
+        if ((h->d.flags & CMPC_ROUNDS_RESELECT) &&
+            (rc = cmpc_nbr_select_dev(ctx, &sd, h->traj_all, h->nbr, nullptr, s)) != CMPC_OK)
+            return rc;
         if ((rc = cmpc_lpv_gather_dev(ctx, &rd, h->nbr, h->traj_all, nb ? h->x_agents : nullptr, h->pose, s)) != CMPC_OK)
             return rc;
         const cmpc_lpv_dims ld{h->d.batch, h->d.N, nb, h->last_rows};

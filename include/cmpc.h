@@ -44,7 +44,9 @@ extern "C" {
 
 #define CMPC_ABI_VERSION 6   /* 2: cmpc_lpv_advance_dev status / infeasible, cmpc_lpv_rounds_*; 3: cmpc_opts.order;
                                 4: cmpc_comm_sum_i32, cmpc_plan_mpc; 5: CMPC_FLAG_POLISH;
-                                6: cmpc_plan_info waves_per_agent / polish_lds_bytes / polish_max_active */
+                                6: cmpc_plan_info waves_per_agent / polish_lds_bytes / polish_max_active;
+                                still 6 (additions only: no struct grew, no entry point changed):
+                                cmpc_nbr_select_dev, CMPC_ROUNDS_RESELECT */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -368,6 +370,37 @@ int cmpc_lpv_advance_dev(cmpc_ctx* ctx, const cmpc_di_dims* dims, const double* 
                          void* hip_stream);
 
 /* ------------------------------------------------------------------------
+ * Neighbour selection on the device, DEVICE pointers, stream-ordered, no host synchronisation.
+ * The reference fixes each agent's neighbour list ns[i] once (LPV_HP_N_main.py:82-85: all other
+ * agents); a population with nb < n_total - 1 whose agents overtake each other needs the list of a
+ * round rebuilt from the exchange buffer every rank already holds.  For every local agent b (global
+ * index g = self_offset + b) the nb nearest other agents out of the n_total trajectories of traj_all
+ * (n_total x (N+1) x 2):
+ *   score(g, j) = min over k in [k0, k1] of (dx dx + dy dy),  dx = traj_all[j,k,0] - traj_all[g,k,0],
+ *     dy likewise, each expression rounded as written (no fma: the bits of numpy's dx*dx + dy*dy);
+ *     a NaN at any stage of the window makes the score NaN (numpy's min), and a NaN score counts as +inf;
+ *   window (0, 0): nearest now; (0, N): closest predicted approach;
+ *   candidates are ordered by (score, j) ascending; j = g is left out by index, never by distance
+ *     (an agent on the same point is a valid neighbour; g itself is never returned: the row builders
+ *     divide by the distance to a neighbour);
+ *   nbr[b, 0..nb) <- their global indices, nearest first; dist2[b, 0..nb) (may be NULL) <- their scores.
+ * The result is fully determined by this rule, ties and non-finite coordinates included
+ * (cmpc.scenarios.select_neighbours is its numpy statement).  The reference's ns[i] is in index
+ * order; nearest first only reorders the collision rows of an agent's QP and the columns of `planes`.
+ * CMPC_ERR_ARG: NULL dims or traj_all, or NULL nbr when batch * nb > 0; nb < 0, nb > CMPC_MAX_MC - 4 or
+ * nb >= n_total; self_offset < 0 or self_offset + batch > n_total; batch < 0; N < 1; a window outside
+ * 0 <= k0 <= k1 <= N.  batch == 0 or nb == 0: CMPC_OK without a launch.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+    int batch, N, nb, self_offset;   /* as cmpc_di_dims */
+    int n_total;                     /* trajectories in traj_all */
+    int k0, k1;                      /* stage window, 0 <= k0 <= k1 <= N */
+} cmpc_nbr_dims;
+int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* dims, const double* traj_all,
+                        int* nbr /* batch x nb */, double* dist2 /* batch x nb, may be NULL */,
+                        void* hip_stream);
+
+/* ------------------------------------------------------------------------
  * Consensus rounds behind a handle (LPV_HP_N_main.py:96-117; the one-process-per-agent ROS
  * variant ROS/src/planner_experiments/src/LPV_ROS_main.py:66-77,124-150), for hosts without
  * torch or device memory of their own (MATLAB through the MEX gateway, plain C).  The handle
@@ -396,6 +429,11 @@ typedef struct cmpc_lpv_rounds cmpc_lpv_rounds;
 
 #define CMPC_ROUNDS_HOST_EXCHANGE 1  /* the host exchanges positions between steps */
 #define CMPC_ROUNDS_NO_HALT 2        /* run all requested rounds even after an infeasible agent */
+#define CMPC_ROUNDS_RESELECT 4       /* every round starts with cmpc_nbr_select_dev, window (0, 0), on the exchange
+                                        buffer as the last exchange / cmpc_lpv_rounds_set_traj left it, into the
+                                        handle's neighbour table (init->nbr is then only the table's first content,
+                                        replaced before it is read; needs nb < n_total).  Off: the table of
+                                        init->nbr for good, as the reference */
 
 typedef struct {
     int n_total;      /* agents over all ranks */
