@@ -135,6 +135,21 @@ class cmpc_lpv_rounds_out(ct.Structure):
     _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("planes", _DP)]
 
 
+CMPC_ROUNDS_LPT = 8        # cmpc_di_rounds: launch order = cmpc_order_by_iters_dev of the previous round's iterations
+
+
+class cmpc_di_rounds_dims(ct.Structure):
+    _fields_ = [(k, ct.c_int) for k in ("n_total", "batch", "self_offset", "N", "nb", "flags", "history")]
+
+
+class cmpc_di_rounds_init(ct.Structure):
+    _fields_ = [("A", _DP), ("B", _DP), ("x0", _DP), ("u_prev", _DP), ("lane", _DP), ("nbr", _IP), ("traj", _DP)]
+
+
+class cmpc_di_rounds_out(ct.Structure):
+    _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP)]
+
+
 class cmpc_qp_dims(ct.Structure):
     _fields_ = [(k, ct.c_int) for k in ("n", "m_ineq", "m_eq", "batch", "col_major")]
 
@@ -226,6 +241,16 @@ SIGNATURES = {
     "cmpc_lpv_rounds_get_traj": (ct.c_int, [ct.c_void_p, _DP]),
     "cmpc_lpv_rounds_set_traj": (ct.c_int, [ct.c_void_p, _DP]),
     "cmpc_lpv_rounds_destroy": (ct.c_int, [ct.c_void_p]),
+    "cmpc_order_by_iters_dev": (ct.c_int, [ct.c_void_p, ct.c_int, _IP, _IP, ct.c_void_p]),
+    "cmpc_di_rounds_create": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_di_params), ct.POINTER(cmpc_mpc_weights),
+                                         ct.POINTER(cmpc_di_rounds_dims), ct.POINTER(cmpc_di_rounds_init),
+                                         ct.POINTER(cmpc_opts), ct.POINTER(ct.c_void_p)]),
+    "cmpc_di_rounds_step": (ct.c_int, [ct.c_void_p, ct.c_int, _IP]),
+    "cmpc_di_rounds_read": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_di_rounds_out)]),
+    "cmpc_di_rounds_history": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _DP, _IP, _IP]),
+    "cmpc_di_rounds_get_traj": (ct.c_int, [ct.c_void_p, _DP]),
+    "cmpc_di_rounds_set_traj": (ct.c_int, [ct.c_void_p, _DP]),
+    "cmpc_di_rounds_destroy": (ct.c_int, [ct.c_void_p]),
 }
 
 CMPC_COMM_ID_BYTES = 128

@@ -90,6 +90,32 @@ def select_neighbours_dev(traj_all, nb, batch=None, self_offset=0, window=(0, 0)
     return out
 
 
+def order_by_iters_dev(iters, out=None, ctx=None, stream=None):
+    """The longest-first launch order of ``cmpc_opts.order`` from a round's per-agent IPM iteration counts
+    ``iters`` (batch,), a contiguous int32 CUDA tensor — one launch of cmpc_order_by_iters_dev on ``stream``
+    (default: torch's current one), no host synchronisation.  The rule is ``scenarios.order_by_iters``'s
+    (descending min(max(iters, 0), 65535), equal keys in index order), the result equal to it and always a
+    permutation.  Writes the (batch,) int32 order into ``out`` (allocated when None; it must not alias
+    ``iters``) and returns it."""
+    import torch
+
+    if not isinstance(iters, torch.Tensor) or iters.dim() != 1 or iters.dtype != torch.int32 or not iters.is_cuda or \
+            not iters.is_contiguous():
+        raise ValueError("iters: a contiguous (batch,) int32 CUDA tensor")
+    batch = int(iters.shape[0])
+    if out is None:
+        out = torch.empty(batch, dtype=torch.int32, device=iters.device)
+    if not isinstance(out, torch.Tensor) or out.device != iters.device or out.dtype != torch.int32 or \
+            tuple(out.shape) != (batch,) or not out.is_contiguous():
+        raise ValueError(f"out: need a contiguous ({batch},) torch.int32 tensor on {iters.device}")
+    ctx = ctx or L.default_context(iters.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(iters.device)
+    ctx.check(ctx.lib.cmpc_order_by_iters_dev(ctx.h, batch, _tptr(iters), _tptr(out),
+                                              ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+    return out
+
+
 class DIRounds:
     """Device-resident consensus rounds of the synthetic double-integrator agents (module docstring).
 
@@ -493,6 +519,93 @@ class LPVRoundsHandle:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.cmpc_lpv_rounds_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DIRoundsHandle:
+    """``DIRounds.step()`` (fused) through the C ABI's round handle (cmpc_di_rounds_*): the library owns the
+    device state; no torch.  What a MATLAB (MEX) or C host drives for the synthetic family.  ``scen``: a
+    ``scenarios.DIScenario``; ``rank`` / ``world``: this handle's contiguous shard, exchanged over the
+    context's communicator or, with ``host_exchange``, by the caller between steps (get_traj / set_traj).
+    ``reselect``: CMPC_ROUNDS_RESELECT, as ``DIRounds(reselect=1)``.  ``lpt``: CMPC_ROUNDS_LPT, the launch
+    order from the previous round's iteration counts on the device (None: ``DIRounds``'s default rule).
+    ``history``: rounds of kkt / iters / status the device ring keeps (``history()``)."""
+
+    def __init__(self, scen, rank=0, world=1, ctx=None, tol=None, max_iter=None, fp32=False, host_exchange=False,
+                 reselect=False, lpt=None, history=1):
+        from .solver import FP32_TOL
+
+        if scen.n_agents % world:
+            raise ValueError("n_agents must be divisible by the number of ranks")
+        self.ctx = ctx or L.default_context(0)
+        sl = scen.shard(rank, world)
+        sh = scen.shared
+        self.B, self.n, self.N, self.nb = sl.stop - sl.start, scen.n_agents, scen.N, scen.nb
+        self.nx, self.nu, self.nz = sh["nx"], sh["nu"], nz_of(sh)
+        ric32 = (sh["nx"], sh["nu"], sh["mc"]) == (6, 3, 6)   # DIRounds's rule
+        self.lpt = (self.N * sh["nu"] > 64 and (not fp32 or ric32)) if lpt is None else bool(lpt)
+        flags = (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (L.CMPC_ROUNDS_RESELECT if reselect else 0) | \
+            (L.CMPC_ROUNDS_LPT if self.lpt else 0)
+        self.dims = L.cmpc_di_rounds_dims(self.n, self.B, sl.start, self.N, self.nb, flags, int(history))
+        p = scen.params
+        prm = L.cmpc_di_params(int(p["dim"]), *(float(p[k]) for k in ("v_ref", "q_v", "q_lane", "hw", "min_vel",
+                                                                        "max_vel", "min_dist", "wq")))
+        w, wkeep = _weights(sh)
+        keep = [L.f64(scen.A[sl]), L.f64(scen.B[sl]), L.f64(scen.x0[sl]), L.f64(scen.u_prev[sl]), L.f64(scen.lane[sl]),
+                L.i32(scen.nbr[sl]), L.f64(scen.traj)]
+        init = L.cmpc_di_rounds_init(*[L.dptr(a) for a in keep[:5]], L.iptr(keep[5]), L.dptr(keep[6]))
+        opts = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, L.CMPC_FLAG_FP32 if fp32 else 0)
+        h = ct.c_void_p()
+        self.ctx.check(self.ctx.lib.cmpc_di_rounds_create(self.ctx.h, ct.byref(prm), ct.byref(w), ct.byref(self.dims),
+                                                          ct.byref(init), ct.byref(opts), ct.byref(h)))
+        self.h = h
+
+    def step(self, rounds=1):
+        """Runs ``rounds`` rounds (one host synchronisation, at the end); returns the number done."""
+        done = ct.c_int()
+        self.ctx.check(self.ctx.lib.cmpc_di_rounds_step(self.h, int(rounds), ct.byref(done)))
+        return done.value
+
+    def read(self):
+        """The latest round: dict of z, kkt, iters, status, x0, u_prev (the next round's), nbr."""
+        r = dict(z=np.zeros((self.B, self.nz)), kkt=np.zeros(self.B), iters=np.zeros(self.B, np.int32),
+                 status=np.zeros(self.B, np.int32), x0=np.zeros((self.B, self.nx)), u_prev=np.zeros((self.B, self.nu)),
+                 nbr=np.zeros((self.B, self.nb), np.int32))
+        o = L.cmpc_di_rounds_out(L.dptr(r["z"]), L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]),
+                                 L.dptr(r["x0"]), L.dptr(r["u_prev"]), L.iptr(r["nbr"]) if self.nb else None)
+        self.ctx.check(self.ctx.lib.cmpc_di_rounds_read(self.h, ct.byref(o)))
+        return r
+
+    def history(self, first, count):
+        """kkt, iters, status of rounds [first, first + count) (counted from create), each (count, B); a round
+        not yet run or already overwritten raises CmpcError(CMPC_ERR_ARG)."""
+        count = int(count)
+        r = dict(kkt=np.zeros((max(count, 0), self.B)), iters=np.zeros((max(count, 0), self.B), np.int32),
+                 status=np.zeros((max(count, 0), self.B), np.int32))
+        self.ctx.check(self.ctx.lib.cmpc_di_rounds_history(self.h, int(first), count, L.dptr(r["kkt"]),
+                                                           L.iptr(r["iters"]), L.iptr(r["status"])))
+        return r
+
+    def get_traj(self):
+        t = np.zeros((self.B, self.N + 1, 2))
+        self.ctx.check(self.ctx.lib.cmpc_di_rounds_get_traj(self.h, L.dptr(t)))
+        return t
+
+    def set_traj(self, traj_all):
+        t = L.f64(traj_all)
+        if t.shape != (self.n, self.N + 1, 2):
+            raise ValueError("traj_all: (n_total, N+1, 2)")
+        self.ctx.check(self.ctx.lib.cmpc_di_rounds_set_traj(self.h, L.dptr(t)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.cmpc_di_rounds_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -127,6 +127,14 @@ def select_neighbours(traj, nb, window=(0, 0), rows=None, return_dist2=False):
     return (idx, np.take_along_axis(score, order, axis=1)) if return_dist2 else idx
 
 
+def order_by_iters(iters):
+    """Host statement of the device launch order (cmpc_order_by_iters_dev, include/cmpc.h): the agents by
+    descending key = min(max(iters, 0), 65535), equal keys in index order — the permutation
+    ``cmpc_opts.order`` takes (last round's longest solves first).  For keys in range it is
+    ``torch.argsort(iters, descending=True, stable=True)``.  Returns (len(iters),) int32."""
+    return np.argsort(-np.clip(np.asarray(iters, np.int64), 0, 65535), kind="stable").astype(np.int32)
+
+
 def make_di(n_agents, N, nb=2, dim=2, seed=SEED):
     rng = np.random.default_rng(seed)
     nx, nu = 2 * dim, dim

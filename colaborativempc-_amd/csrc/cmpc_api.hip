@@ -139,6 +139,7 @@ int cmpc_destroy(cmpc_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
     if (ctx->ws) (void)hipFree(ctx->ws);
+    if (ctx->order_ws) (void)hipFree(ctx->order_ws);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return CMPC_OK;
@@ -385,6 +386,35 @@ int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* tra
     if (rc != CMPC_OK) return rc;
     const cmpc::NbrConst c{d->batch, d->N, d->nb, d->self_offset, d->n_total, d->k0, d->k1};
     HIP_TRY(cmpc::nbr_select_launch(c, traj_all, nbr, dist2, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
+int cmpc_order_by_iters_dev(cmpc_ctx* ctx, int batch, const int* iters, int* order, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (batch < 0) return fail(ctx, CMPC_ERR_ARG, "negative batch");
+    if (batch == 0) return CMPC_OK;
+    if (!iters || !order) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    if (order < iters + batch && iters < order + batch)
+        return fail(ctx, CMPC_ERR_ARG, "order must not alias iters (the sort is not in place)");
+    int rc = set_device(ctx);
+    if (rc != CMPC_OK) return rc;
+    const size_t bytes = 8 * (size_t)batch;
+    if (ctx->order_ws_bytes < bytes) {  // first use, or a larger batch: a steady-state call allocates nothing
+        if (ctx->order_ws) {
+            (void)hipDeviceSynchronize();  // queued launches may still use the old scratch
+            (void)hipFree(ctx->order_ws);
+            ctx->order_ws = nullptr;
+            ctx->order_ws_bytes = 0;
+        }
+        const size_t want = bytes + bytes / 4 + 4096;
+        if (hipMalloc(&ctx->order_ws, want) != hipSuccess) {
+            ctx->order_ws = nullptr;
+            return fail(ctx, CMPC_ERR_NOMEM, "device scratch allocation failed");
+        }
+        ctx->order_ws_bytes = want;
+    }
+    HIP_TRY(cmpc::order_launch(batch, iters, order, reinterpret_cast<unsigned long long*>(ctx->order_ws),
+                               (hipStream_t)stream));
     return CMPC_OK;
 }
 

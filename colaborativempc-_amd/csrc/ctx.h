@@ -12,6 +12,8 @@ struct cmpc_ctx {
     hipStream_t stream = nullptr;  // private stream for the host-pointer entry points
     char* ws = nullptr;            // device arena
     size_t ws_bytes = 0;
+    char* order_ws = nullptr;      // scratch of cmpc_order_by_iters_dev (its own: the arena belongs to the solvers)
+    size_t order_ws_bytes = 0;
     ncclComm_t comm = nullptr;     // RCCL communicator of cmpc_comm_init (multi-GPU exchange)
     int nranks = 1, rank = 0;      // of that communicator
     std::string err;

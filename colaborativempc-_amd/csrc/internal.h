@@ -257,6 +257,10 @@ struct NbrConst {
 };
 hipError_t nbr_select_launch(const NbrConst& c, const double* traj_all, int* nbr, double* dist2, hipStream_t s);
 
+// Launch order (order.hip): order <- the agents by descending min(max(iters, 0), 65535), ties by ascending
+// index; tmp: batch x 8 bytes of device scratch.  One workgroup; nothing is launched for batch <= 0
+hipError_t order_launch(int batch, const int* iters, int* order, unsigned long long* tmp, hipStream_t s);
+
 // Synthetic double-integrator family (bench workload).
 
 struct DiPtrs {

@@ -5,6 +5,7 @@
 //   [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's
 // communicator (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).
+// cmpc_di_rounds_* (further down) is the same handle for the synthetic double-integrator family.
 #include <cstring>
 
 #include "ctx.h"
@@ -24,9 +25,28 @@ struct cmpc_lpv_rounds {
     int *nbr = nullptr, *iters = nullptr, *status = nullptr, *infeasible = nullptr;
 };
 
+struct cmpc_di_rounds {
+    cmpc_ctx* ctx = nullptr;
+    cmpc_di_params prm{};
+    cmpc_di_rounds_dims d{};  // history >= 1
+    cmpc_mpc_dims md{};
+    cmpc_opts opts{};
+    // copy of the batch-shared weights (cmpc_mpc_weights holds host pointers)
+    double Q[CMPC_MAX_NX * CMPC_MAX_NX]{}, R[CMPC_MAX_NU * CMPC_MAX_NU]{}, dR[CMPC_MAX_NU * CMPC_MAX_NU]{},
+        Qs[CMPC_MAX_NS]{}, u_ub[CMPC_MAX_NU]{}, u_lb[CMPC_MAX_NU]{};
+    int row_slack[CMPC_MAX_MC]{}, row_sign[CMPC_MAX_MC]{};
+    cmpc_mpc_weights w{};
+    int rounds_done = 0;  // since create: round r writes row r % history of kkt / iters / status
+    char* mem = nullptr;
+    double *A = nullptr, *B = nullptr, *x0 = nullptr, *u_prev = nullptr, *lane = nullptr, *traj_all = nullptr,
+           *traj_local = nullptr, *qlin = nullptr, *C = nullptr, *h = nullptr, *z = nullptr, *kkt = nullptr;
+    int *nbr = nullptr, *iters = nullptr, *status = nullptr, *order = nullptr;
+};
+
 namespace {
 
 size_t nz_lpv(int N) { return 12 * (size_t)(N + 1) + 4 * (size_t)N; }
+size_t nz_di(int nx, int nu, int N) { return (size_t)(nx + 3) * (N + 1) + 2 * (size_t)nu * N; }
 
 }  // namespace
 
@@ -231,6 +251,224 @@ int cmpc_lpv_rounds_set_traj(cmpc_lpv_rounds* h, const double* traj_all) {
 }
 
 int cmpc_lpv_rounds_destroy(cmpc_lpv_rounds* h) {
+    if (!h) return CMPC_OK;
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->mem);
+    delete h;
+    return CMPC_OK;
+}
+
+// ---- the synthetic double-integrator family (cmpc_di_rounds_*): what cmpc.rounds.DIRounds.step() chains ----
+//   [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
+
+int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_mpc_weights* w,
+                          const cmpc_di_rounds_dims* dims, const cmpc_di_rounds_init* in, const cmpc_opts* opts,
+                          cmpc_di_rounds** out) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    *out = nullptr;
+    const cmpc_di_rounds_dims& d = *dims;
+    if (d.N < 1 || d.nb < 0 || 4 + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
+        d.self_offset + d.batch > d.n_total)
+        return fail(ctx, CMPC_ERR_ARG, "bad rounds dimensions (1 <= batch, self_offset + batch <= n_total, nb <= 12)");
+    if (prm->dim != 2 && prm->dim != 3) return fail(ctx, CMPC_ERR_ARG, "double-integrator agents have dim 2 or 3");
+    if (d.history < 0) return fail(ctx, CMPC_ERR_ARG, "negative history");
+    if (d.flags & ~(CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT))
+        return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
+    if ((d.flags & CMPC_ROUNDS_RESELECT) && d.nb >= d.n_total)
+        return fail(ctx, CMPC_ERR_ARG, "CMPC_ROUNDS_RESELECT selects nb < n_total neighbours");
+    if (!w->Q || !w->R || !w->dR || !w->Qs || !w->u_ub || !w->u_lb || !w->row_slack || !w->row_sign)
+        return fail(ctx, CMPC_ERR_ARG, "null weights");
+    if (!in->A || !in->B || !in->x0 || !in->u_prev || !in->lane || !in->traj || (d.nb > 0 && !in->nbr))
+        return fail(ctx, CMPC_ERR_ARG, "null initial state");
+    if (d.batch != d.n_total && !(d.flags & CMPC_ROUNDS_HOST_EXCHANGE) &&
+        (!ctx->comm || (long)ctx->nranks * d.batch != d.n_total || ctx->rank * d.batch != d.self_offset))
+        return fail(ctx, CMPC_ERR_ARG,
+                    "a sharded population exchanges over the context's communicator (cmpc_comm_init: equal "
+                    "contiguous shards in rank order) or the host's (CMPC_ROUNDS_HOST_EXCHANGE)");
+    for (int i = 0; in->nbr && i < d.batch * d.nb; ++i)
+        if (in->nbr[i] < 0 || in->nbr[i] >= d.n_total) return fail(ctx, CMPC_ERR_ARG, "neighbour index out of range");
+    if (opts && (opts->flags & ~CMPC_FLAG_ALL)) return fail(ctx, CMPC_ERR_ARG, "unknown option flag");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    auto* h = new cmpc_di_rounds();
+    h->ctx = ctx;
+    h->prm = *prm;
+    h->d = d;
+    if (h->d.history == 0) h->d.history = 1;
+    if (opts) h->opts = *opts;
+    h->opts.stamps = nullptr;
+    h->opts.order = nullptr;
+    const int nx = 2 * prm->dim, nu = prm->dim, mc = 4 + d.nb;
+    h->md = cmpc_mpc_dims{nx, nu, d.N, 3, mc, d.batch};
+    std::memcpy(h->Q, w->Q, sizeof(double) * nx * nx);
+    std::memcpy(h->R, w->R, sizeof(double) * nu * nu);
+    std::memcpy(h->dR, w->dR, sizeof(double) * nu * nu);
+    std::memcpy(h->Qs, w->Qs, sizeof(double) * 3);
+    std::memcpy(h->u_ub, w->u_ub, sizeof(double) * nu);
+    std::memcpy(h->u_lb, w->u_lb, sizeof(double) * nu);
+    std::memcpy(h->row_slack, w->row_slack, sizeof(int) * mc);
+    std::memcpy(h->row_sign, w->row_sign, sizeof(int) * mc);
+    h->w = cmpc_mpc_weights{h->Q, h->R, h->dR, h->Qs, h->u_ub, h->u_lb, h->row_slack, h->row_sign};
+
+    const size_t B = d.batch, N = d.N, nb = d.nb, T = d.n_total, row = (N + 1) * 2, H = h->d.history;
+    const size_t cnt[] = {B * N * nx * nx, B * N * nx * nu, B * nx, B * nu, B, T * row, B * row,
+                          B * (N + 1) * nx, B * N * mc * nx, B * N * mc, B * nz_di(nx, nu, d.N), H * B};
+    size_t bytes = 0;
+    for (size_t c : cnt) bytes += ((8 * c + 255) & ~size_t(255));
+    bytes += ((4 * B * (nb ? nb : 1) + 255) & ~size_t(255)) + 2 * ((4 * H * B + 255) & ~size_t(255)) +
+             ((4 * B + 255) & ~size_t(255));
+    if (hipMalloc(&h->mem, bytes) != hipSuccess) {
+        delete h;
+        return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
+    }
+    size_t off = 0;
+    auto take = [&](size_t b) {
+        char* p = h->mem + off;
+        off += (b + 255) & ~size_t(255);
+        return p;
+    };
+    double** dp[] = {&h->A, &h->B, &h->x0, &h->u_prev, &h->lane, &h->traj_all, &h->traj_local, &h->qlin, &h->C,
+                     &h->h, &h->z, &h->kkt};
+    for (int i = 0; i < 12; ++i) *dp[i] = reinterpret_cast<double*>(take(8 * cnt[i]));
+    h->nbr = reinterpret_cast<int*>(take(4 * B * (nb ? nb : 1)));
+    h->iters = reinterpret_cast<int*>(take(4 * H * B));
+    h->status = reinterpret_cast<int*>(take(4 * H * B));
+    h->order = reinterpret_cast<int*>(take(4 * B));
+
+    hipStream_t s = ctx->stream;
+    auto up = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s); };
+    hipError_t e = hipMemsetAsync(h->mem, 0, bytes, s);  // a read before the first round returns zeros
+    if (e == hipSuccess) e = up(h->A, in->A, 8 * cnt[0]);
+    if (e == hipSuccess) e = up(h->B, in->B, 8 * cnt[1]);
+    if (e == hipSuccess) e = up(h->x0, in->x0, 8 * cnt[2]);
+    if (e == hipSuccess) e = up(h->u_prev, in->u_prev, 8 * cnt[3]);
+    if (e == hipSuccess) e = up(h->lane, in->lane, 8 * cnt[4]);
+    if (e == hipSuccess) e = up(h->traj_all, in->traj, 8 * cnt[5]);
+    if (e == hipSuccess && nb) e = up(h->nbr, in->nbr, 4 * B * nb);
+    // this rank's rows of the exchange buffer until the first round writes them
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h->traj_local, h->traj_all + (size_t)d.self_offset * row, 8 * B * row,
+                           hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipFree(h->mem);
+        delete h;
+        return hip_fail(ctx, e, "cmpc_di_rounds_create: upload");
+    }
+    *out = h;
+    return CMPC_OK;
+}
+
+int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (rounds_done) *rounds_done = 0;
+    if (rounds < 0) return fail(ctx, CMPC_ERR_ARG, "negative round count");
+    const bool host_x = h->d.flags & CMPC_ROUNDS_HOST_EXCHANGE, sharded = h->d.batch != h->d.n_total;
+    if (host_x && sharded && rounds > 1)
+        return fail(ctx, CMPC_ERR_ARG, "host exchange: one round per step (exchange between steps)");
+    const bool lpt = h->d.flags & CMPC_ROUNDS_LPT;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch, row = 2 * (size_t)(h->d.N + 1);
+    const cmpc_di_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset};
+    const cmpc_nbr_dims sd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->d.n_total, 0, 0};
+    const cmpc_mpc_data din{h->A, h->B, h->x0, h->u_prev, h->qlin, h->C, h->h};
+    int done = 0, rc = CMPC_OK;
+    for (int r = 0; r < rounds && rc == CMPC_OK; ++r) {
+        const size_t slot = (size_t)(h->rounds_done % h->d.history) * B;  // this round's row of the history ring
+        const cmpc_mpc_out dout{h->z, h->kkt + slot, h->iters + slot, h->status + slot};
+        if ((h->d.flags & CMPC_ROUNDS_RESELECT) && h->d.nb > 0 &&
+            (rc = cmpc_nbr_select_dev(ctx, &sd, h->traj_all, h->nbr, nullptr, s)) != CMPC_OK)
+            break;
+        h->opts.order = (lpt && h->rounds_done > 0) ? h->order : nullptr;
+        if ((rc = cmpc_di_round_dev(ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w, &din, &dout,
+                                    &h->opts, h->traj_local, s)) != CMPC_OK)
+            break;
+        // the next round's launch order, stream-ordered after this solve
+        if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) break;
+        ++h->rounds_done;  // the round's outputs exist from here on, whatever the exchange returns
+        ++done;
+        if (!sharded) {
+            hipError_t e = hipMemcpyAsync(h->traj_all, h->traj_local, 8 * row * B, hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) rc = hip_fail(ctx, e, "cmpc_di_rounds_step: exchange");
+        } else if (!host_x) {
+            rc = cmpc_allgather_trajectories(ctx, h->traj_local, h->traj_all, row * B, s);
+        }
+    }
+    // one host synchronisation, also after an error: the rounds already queued have then finished
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rounds_done) *rounds_done = done;
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(e);
+    return CMPC_OK;
+}
+
+int cmpc_di_rounds_read(cmpc_di_rounds* h, const cmpc_di_rounds_out* o) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    const size_t slot = (size_t)((h->rounds_done > 0 ? h->rounds_done - 1 : 0) % h->d.history) * B;
+    auto dn = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s); };
+    if (o->z) HIP_TRY(dn(o->z, h->z, 8 * B * nz_di(h->md.nx, h->md.nu, h->d.N)));
+    if (o->kkt) HIP_TRY(dn(o->kkt, h->kkt + slot, 8 * B));
+    if (o->iters) HIP_TRY(dn(o->iters, h->iters + slot, 4 * B));
+    if (o->status) HIP_TRY(dn(o->status, h->status + slot, 4 * B));
+    if (o->x0) HIP_TRY(dn(o->x0, h->x0, 8 * B * h->md.nx));
+    if (o->u_prev) HIP_TRY(dn(o->u_prev, h->u_prev, 8 * B * h->md.nu));
+    if (o->nbr && h->d.nb) HIP_TRY(dn(o->nbr, h->nbr, 4 * B * h->d.nb));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
+int cmpc_di_rounds_history(cmpc_di_rounds* h, int first_round, int count, double* kkt, int* iters, int* status) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (first_round < 0 || count < 0 || (long long)first_round + count > h->rounds_done)
+        return fail(ctx, CMPC_ERR_ARG, "history: a round that has not run yet");
+    if (count > 0 && first_round < h->rounds_done - h->d.history)
+        return fail(ctx, CMPC_ERR_ARG, "history: a round the ring has already overwritten (dims.history rounds are kept)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    for (int i = 0; i < count; ++i) {
+        const size_t slot = (size_t)((first_round + i) % h->d.history) * B;
+        if (kkt) HIP_TRY(hipMemcpyAsync(kkt + i * B, h->kkt + slot, 8 * B, hipMemcpyDeviceToHost, s));
+        if (iters) HIP_TRY(hipMemcpyAsync(iters + i * B, h->iters + slot, 4 * B, hipMemcpyDeviceToHost, s));
+        if (status) HIP_TRY(hipMemcpyAsync(status + i * B, h->status + slot, 4 * B, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
+int cmpc_di_rounds_get_traj(cmpc_di_rounds* h, double* traj_local) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!traj_local) return fail(ctx, CMPC_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(traj_local, h->traj_local, 16 * (size_t)(h->d.N + 1) * h->d.batch, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return CMPC_OK;
+}
+
+int cmpc_di_rounds_set_traj(cmpc_di_rounds* h, const double* traj_all) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!traj_all) return fail(ctx, CMPC_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h->traj_all, traj_all, 16 * (size_t)(h->d.N + 1) * h->d.n_total, hipMemcpyHostToDevice,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return CMPC_OK;
+}
+
+int cmpc_di_rounds_destroy(cmpc_di_rounds* h) {
     if (!h) return CMPC_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);

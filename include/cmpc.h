@@ -46,7 +46,8 @@ extern "C" {
                                 4: cmpc_comm_sum_i32, cmpc_plan_mpc; 5: CMPC_FLAG_POLISH;
                                 6: cmpc_plan_info waves_per_agent / polish_lds_bytes / polish_max_active;
                                 still 6 (additions only: no struct grew, no entry point changed):
-                                cmpc_nbr_select_dev, CMPC_ROUNDS_RESELECT */
+                                cmpc_nbr_select_dev, CMPC_ROUNDS_RESELECT; cmpc_order_by_iters_dev,
+                                cmpc_di_rounds_*, CMPC_ROUNDS_LPT */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -401,6 +402,22 @@ int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* dims, const double* 
                         void* hip_stream);
 
 /* ------------------------------------------------------------------------
+ * The longest-first launch order of cmpc_opts.order, on the device: DEVICE pointers, stream-ordered, no
+ * host synchronisation.
+ *   order[0..batch) <- the agents by descending key, ties by ascending index (a stable sort):
+ *     key(b) = min(max(iters[b], 0), 65535)
+ * with iters the previous round's per-agent IPM iteration counts (cmpc_mpc_out.iters).  Always a
+ * permutation of 0..batch-1, whatever iters holds (cmpc_opts.order requires one: a non-permutation is a
+ * data race).  For keys in range it is torch.argsort(iters, descending=True, stable=True);
+ * cmpc.scenarios.order_by_iters is its numpy statement.  One workgroup (a two-pass 8-bit radix sort of
+ * (key, index); its launch time beside a round's solver launch: DESIGN.md section 4).  Its scratch (8 bytes
+ * per agent) belongs to the context and grows on first use; a steady-state call allocates nothing.
+ * order must not alias iters (CMPC_ERR_ARG).  batch == 0: CMPC_OK without a launch.  NULL pointers with
+ * batch > 0, batch < 0: CMPC_ERR_ARG.
+ * ---------------------------------------------------------------------- */
+int cmpc_order_by_iters_dev(cmpc_ctx* ctx, int batch, const int* iters, int* order, void* hip_stream);
+
+/* ------------------------------------------------------------------------
  * Consensus rounds behind a handle (LPV_HP_N_main.py:96-117; the one-process-per-agent ROS
  * variant ROS/src/planner_experiments/src/LPV_ROS_main.py:66-77,124-150), for hosts without
  * torch or device memory of their own (MATLAB through the MEX gateway, plain C).  The handle
@@ -475,6 +492,79 @@ int cmpc_lpv_rounds_get_traj(cmpc_lpv_rounds* h, double* traj_local);
 int cmpc_lpv_rounds_set_traj(cmpc_lpv_rounds* h, const double* traj_all);
 /* Destroy every handle of a context before cmpc_destroy(ctx). */
 int cmpc_lpv_rounds_destroy(cmpc_lpv_rounds* h);
+
+/* ------------------------------------------------------------------------
+ * The same handle for the synthetic double-integrator family (cmpc_di_params; BASELINE cfg2-cfg5): what
+ * cmpc.rounds.DIRounds.step() does with fused=True, launch for launch and bit for bit, for hosts without
+ * torch or device memory of their own.  A round, on the context's stream:
+ *   1. CMPC_ROUNDS_RESELECT and nb > 0: cmpc_nbr_select_dev, window (0, 0), into the handle's table;
+ *   2. cmpc_di_round_dev on the handle's buffers (build, solve and advance in one launch where the v3
+ *      kernel covers the problem; build, solve and advance launches elsewhere); with CMPC_ROUNDS_LPT, from
+ *      the second round on, cmpc_opts.order = the handle's order buffer;
+ *   3. CMPC_ROUNDS_LPT: cmpc_order_by_iters_dev of this round's iteration counts into the order buffer;
+ *   4. the exchange, as cmpc_lpv_rounds_step: a device copy (one rank), the context's RCCL communicator
+ *      (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE: one round per step,
+ *      cmpc_di_rounds_get_traj / _set_traj in between).
+ * The synthetic family has no halt rule: cmpc_di_rounds_step always runs the rounds it is asked for.
+ * opts->flags go to the solver unchanged (CMPC_FLAG_FP32, the wave flags, ...); opts->stamps and
+ * opts->order are ignored.  Dimension and flag combinations the solver refuses come back from the first
+ * cmpc_di_rounds_step with the solver's own code and message.
+ *
+ * History: round r (counted from create) writes its kkt / iters / status into row r mod `history` of a
+ * device ring — the solver's output pointers are set to that row, nothing is copied — so a host that calls
+ * cmpc_di_rounds_step(h, 100, ...) once still gets every round's statuses and iteration counts
+ * (cmpc_di_rounds_history) without one host synchronisation per round.
+ *
+ * CMPC_ERR_ARG at create: a NULL argument (opts may be NULL; init->nbr may be NULL when nb == 0); batch < 1,
+ * self_offset < 0 or self_offset + batch > n_total; N < 1; dim not 2 or 3; nb < 0 or 4 + nb > CMPC_MAX_MC; a
+ * neighbour index outside 0 <= j < n_total; CMPC_ROUNDS_RESELECT with nb >= n_total; a sharded population
+ * (batch != n_total) without CMPC_ROUNDS_HOST_EXCHANGE and without a matching communicator (cmpc_comm_init:
+ * equal contiguous shards in rank order); history < 0; an unknown rounds or option flag.
+ * ---------------------------------------------------------------------- */
+typedef struct cmpc_di_rounds cmpc_di_rounds;
+
+#define CMPC_ROUNDS_LPT 8   /* from the second round on, cmpc_opts.order = cmpc_order_by_iters_dev of the previous
+                               round's iteration counts (the first round: NULL, identity).  Only when an agent
+                               runs changes, never what it returns.  cmpc_di_rounds only */
+
+typedef struct {
+    int n_total, batch, self_offset;  /* as cmpc_lpv_rounds_dims */
+    int N, nb;
+    int flags;      /* CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT; CMPC_ROUNDS_NO_HALT is
+                       accepted and has no effect (the synthetic family has no halt rule); other bits CMPC_ERR_ARG */
+    int history;    /* rounds of per-agent kkt / iters / status kept on the device, >= 1 (0 selects 1) */
+} cmpc_di_rounds_dims;
+
+typedef struct {    /* HOST pointers, this rank's agents, copied at create: what cmpc.scenarios.make_di produces */
+    const double *A, *B;        /* batch x N x nx x nx, batch x N x nx x nu   (nx = 2 dim, nu = dim) */
+    const double *x0, *u_prev;  /* batch x nx, batch x nu */
+    const double* lane;         /* batch */
+    const int* nbr;             /* batch x nb global indices (checked: 0 <= j < n_total) */
+    const double* traj;         /* n_total x (N+1) x 2 initial exchange buffer (required) */
+} cmpc_di_rounds_init;
+
+typedef struct {    /* HOST pointers, any may be NULL: the latest round of this rank's agents */
+    double *z, *kkt;            /* batch x nz (nz = (nx + 3)(N+1) + 2 nu N), batch */
+    int *iters, *status;        /* batch */
+    double *x0, *u_prev;        /* batch x nx, batch x nu: the next round's initial state and previous input */
+    int* nbr;                   /* batch x nb: the table the latest round used */
+} cmpc_di_rounds_out;
+
+/* w: ns = 3 slacks and mc = 4 + nb rows (Q nx*nx, R / dR nu*nu, Qs 3, u_ub / u_lb nu, row_slack / row_sign
+ * 4 + nb), copied at create. */
+int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_mpc_weights* w,
+                          const cmpc_di_rounds_dims* dims, const cmpc_di_rounds_init* init, const cmpc_opts* opts,
+                          cmpc_di_rounds** out);
+/* Runs `rounds` rounds (*rounds_done, may be NULL: the number completed); synchronises the host once, at the end. */
+int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done);
+int cmpc_di_rounds_read(cmpc_di_rounds* h, const cmpc_di_rounds_out* host_out);
+/* Rounds [first_round, first_round + count) of the ring as count x batch arrays (any may be NULL).  A round not
+ * yet run, or already overwritten (older than the last `history` rounds): CMPC_ERR_ARG. */
+int cmpc_di_rounds_history(cmpc_di_rounds* h, int first_round, int count, double* kkt, int* iters, int* status);
+int cmpc_di_rounds_get_traj(cmpc_di_rounds* h, double* traj_local);
+int cmpc_di_rounds_set_traj(cmpc_di_rounds* h, const double* traj_all);
+/* Destroy every handle of a context before cmpc_destroy(ctx). */
+int cmpc_di_rounds_destroy(cmpc_di_rounds* h);
 
 
 /* ------------------------------------------------------------------------
