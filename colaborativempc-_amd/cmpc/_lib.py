@@ -150,6 +150,22 @@ class cmpc_di_rounds_out(ct.Structure):
     _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP)]
 
 
+class cmpc_log_dims(ct.Structure):
+    _fields_ = [(k, ct.c_int) for k in ("batch", "nx", "nu", "ns", "N", "look_col")]
+
+
+class cmpc_log_row(ct.Structure):   # device pointers to one round's rows
+    _fields_ = [("state", _DP), ("u", _DP), ("look_ahead", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP)]
+
+
+CMPC_LOG_SEPARATION = 1    # the log also keeps each agent's nearest other agent and the squared distance
+
+
+class cmpc_rounds_log(ct.Structure):   # host pointers, leading dimension = count
+    _fields_ = [("state", _DP), ("u", _DP), ("look_ahead", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP),
+                ("sep2", _DP), ("nearest", _IP), ("solve_ms", _DP)]
+
+
 class cmpc_qp_dims(ct.Structure):
     _fields_ = [(k, ct.c_int) for k in ("n", "m_ineq", "m_eq", "batch", "col_major")]
 
@@ -251,6 +267,14 @@ SIGNATURES = {
     "cmpc_di_rounds_get_traj": (ct.c_int, [ct.c_void_p, _DP]),
     "cmpc_di_rounds_set_traj": (ct.c_int, [ct.c_void_p, _DP]),
     "cmpc_di_rounds_destroy": (ct.c_int, [ct.c_void_p]),
+    "cmpc_round_log_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_log_dims), _DP, _DP, _IP, _IP,
+                                      ct.POINTER(cmpc_log_row), ct.c_void_p]),
+    "cmpc_lpv_rounds_log_enable": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
+    "cmpc_lpv_rounds_log_range": (ct.c_int, [ct.c_void_p, _IP, _IP]),
+    "cmpc_lpv_rounds_log_read": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_rounds_log)]),
+    "cmpc_di_rounds_log_enable": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
+    "cmpc_di_rounds_log_range": (ct.c_int, [ct.c_void_p, _IP, _IP]),
+    "cmpc_di_rounds_log_read": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_rounds_log)]),
 }
 
 CMPC_COMM_ID_BYTES = 128

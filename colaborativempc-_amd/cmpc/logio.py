@@ -4,6 +4,7 @@
 * ``save_to_csv``: <path_csv>/csv/<id>/{states,u,plan_dist,time}.dat (+ time_OCD.dat,
   OCD_it.dat for OCD runs) as ``np.savetxt(fmt='%.5e', delimiter=' ')``
   (plan_lib/config/base_class.py:64-99, with time / time_OCD of :143-166).
+* ``save_run``: those four files for every agent of a round handle's device log (cmpc_*_rounds_log_read).
 * ``save_settings``: settings.csv, one ``key,value`` row per config entry (utilities/misc.py:264-275).
 * ``serialise_np`` / ``deserialise_np``: the ROS ``agent_info`` payload (a list of float32
   arrays with their shapes; ROS/src/planner_experiments/src/utilities_ROS/utilities_ros.py:7-45),
@@ -55,6 +56,18 @@ def save_to_csv(path_csv, agent_id, states, u, look_ahead, time_op, ocd_it=None)
     else:
         np.savetxt(os.path.join(path, "time.dat"), np.asarray(time_op), fmt=FMT, delimiter=" ")
     return path
+
+
+def save_run(path_csv, log, first_agent_id=0):
+    """The reference's four log files of every agent from a round handle's log (``LPVRoundsHandle.log()`` /
+    ``DIRoundsHandle.log()``: arrays with the round as leading dimension): agent column b goes to
+    <path_csv>/csv/<first_agent_id + b>/ through ``save_to_csv`` — states.dat row r = xPred[0] of round r, u.dat
+    uPred[0], plan_dist.dat the look-ahead.  time.dat is in seconds, as the reference's: ``log["solve_ms"]`` /
+    1e3, the whole batch's solver launch, so the same column for every agent of the rank.  Returns the
+    directories written."""
+    t = np.asarray(log["solve_ms"]) / 1e3
+    return [save_to_csv(path_csv, first_agent_id + b, log["state"][:, b], log["u"][:, b], log["look_ahead"][:, b], t)
+            for b in range(np.asarray(log["state"]).shape[1])]
 
 
 def save_settings(path, settings):

@@ -116,6 +116,90 @@ def order_by_iters_dev(iters, out=None, ctx=None, stream=None):
     return out
 
 
+def log_round_dev(z, nx, nu, ns, N, look_col, row=None, kkt=None, iters=None, status=None, ctx=None, stream=None):
+    """A round's log rows on the device — one launch of cmpc_round_log_dev on ``stream`` (default: torch's current
+    one), no host synchronisation: out of the round's ``z`` (batch, nz), a contiguous fp64 CUDA tensor in the
+    reference layout, ``row["state"]`` (batch, nx) <- xPred[0], ``row["u"]`` (batch, nu) <- uPred[0],
+    ``row["look_ahead"]`` (batch,) <- xPred[-1, look_col] - xPred[0, look_col], and ``row["kkt" | "iters" |
+    "status"]`` (batch,) <- the solver outputs ``kkt`` / ``iters`` / ``status`` of the round — the rule of
+    ``scenarios.log_row``, bit for bit.  ``row``: dict of destination tensors, e.g. one row per round of a
+    preallocated history; a key that is missing or None is skipped.  None: state, u and look_ahead are
+    allocated, and kkt / iters / status where the source is given.  Returns ``row``.  What the round handles do
+    with ``log=``; the torch-driven ``LPVRounds`` / ``DIRounds`` hold their tensors and call this."""
+    import torch
+
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.dtype != torch.float64 or not z.is_cuda or \
+            not z.is_contiguous():
+        raise ValueError("z: a contiguous (batch, nz) float64 CUDA tensor")
+    batch = int(z.shape[0])
+    if z.shape[1] != (nx + ns) * (N + 1) + 2 * nu * N:
+        raise ValueError("z: nz = (nx+ns)(N+1) + 2 nu N")
+    shapes = dict(state=((batch, nx), torch.float64), u=((batch, nu), torch.float64),
+                  look_ahead=((batch,), torch.float64), kkt=((batch,), torch.float64),
+                  iters=((batch,), torch.int32), status=((batch,), torch.int32))
+    src = dict(kkt=kkt, iters=iters, status=status)
+    if row is None:
+        row = {k: torch.empty(shp, dtype=dt, device=z.device) for k, (shp, dt) in shapes.items()
+               if k not in src or src[k] is not None}
+    for k, t in list(row.items()) + list(src.items()):
+        if k not in shapes:
+            raise ValueError(f"row: unknown destination {k!r}")
+        shp, dt = shapes[k]
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != z.device or t.dtype != dt or
+                              tuple(t.shape) != shp or not t.is_contiguous()):
+            raise ValueError(f"{k}: need a contiguous {shp} {dt} tensor on {z.device}")
+    if batch == 0:   # empty tensors have no address to hand over; the entry point launches nothing either
+        return row
+    ctx = ctx or L.default_context(z.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(z.device)
+    dims = L.cmpc_log_dims(batch, int(nx), int(nu), int(ns), int(N), int(look_col))
+    dst = L.cmpc_log_row(*[_tptr(row.get(k)) for k in ("state", "u", "look_ahead", "kkt", "iters", "status")])
+    ctx.check(ctx.lib.cmpc_round_log_dev(ctx.h, ct.byref(dims), _tptr(z), _tptr(kkt), _tptr(iters), _tptr(status),
+                                         ct.byref(dst), ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+    return row
+
+
+class _HandleLog:
+    """The device log of a round handle (cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, include/cmpc.h); the
+    handle class sets ``_log_fn`` (the entry points' common prefix) and ``_log_nx`` / ``_log_nu``."""
+
+    def _log_enable(self, capacity, separation):
+        self.log_separation = bool(separation)
+        if capacity or separation:
+            fn = getattr(self.ctx.lib, self._log_fn + "enable")
+            self.ctx.check(fn(self.h, int(capacity), L.CMPC_LOG_SEPARATION if separation else 0))
+
+    def log_range(self):
+        """(first, count): the rounds the log ring holds now, counted from create."""
+        first, count = ct.c_int(), ct.c_int()
+        self.ctx.check(getattr(self.ctx.lib, self._log_fn + "range")(self.h, ct.byref(first), ct.byref(count)))
+        return first.value, count.value
+
+    def log(self, first=None, count=None):
+        """Rounds [first, first + count) of the log (default: everything the ring holds) as a dict of arrays with
+        leading dimension ``count``: state (count, B, nx) = xPred[0], u (count, B, nu) = uPred[0], look_ahead,
+        kkt, iters, status (count, B), solve_ms (count,): the whole batch's solver launch of the round, in
+        milliseconds; with ``log_separation`` nearest (count, B) int32, each agent's nearest other agent after
+        the round's exchange, and sep2 the squared distance.  ``logio.save_run`` writes it as the reference's
+        csv/<id>/*.dat.  A round outside the ring raises CmpcError(CMPC_ERR_ARG)."""
+        if first is None or count is None:
+            lo, n = self.log_range()
+            first = lo if first is None else first
+            count = lo + n - first if count is None else count
+        c = max(int(count), 0)
+        r = dict(state=np.zeros((c, self.B, self._log_nx)), u=np.zeros((c, self.B, self._log_nu)),
+                 look_ahead=np.zeros((c, self.B)), kkt=np.zeros((c, self.B)), iters=np.zeros((c, self.B), np.int32),
+                 status=np.zeros((c, self.B), np.int32), solve_ms=np.zeros(c))
+        if self.log_separation:
+            r.update(sep2=np.zeros((c, self.B)), nearest=np.zeros((c, self.B), np.int32))
+        o = L.cmpc_rounds_log(L.dptr(r["state"]), L.dptr(r["u"]), L.dptr(r["look_ahead"]), L.dptr(r["kkt"]),
+                              L.iptr(r["iters"]), L.iptr(r["status"]), L.dptr(r.get("sep2")), L.iptr(r.get("nearest")),
+                              L.dptr(r["solve_ms"]))
+        self.ctx.check(getattr(self.ctx.lib, self._log_fn + "read")(self.h, int(first), int(count), ct.byref(o)))
+        return r
+
+
 class DIRounds:
     """Device-resident consensus rounds of the synthetic double-integrator agents (module docstring).
 
@@ -457,15 +541,19 @@ class InfeasibleRound(RuntimeError):
         self.count = count
 
 
-class LPVRoundsHandle:
+class LPVRoundsHandle(_HandleLog):
     """The same rounds through the C ABI's round handle (cmpc_lpv_rounds_*): the library owns the
     device state; no torch.  What a MATLAB (MEX) or C host drives.  Arguments as LPVRounds;
     ``host_exchange``: the caller exchanges positions between steps (get_traj / set_traj).  ``reselect``:
     CMPC_ROUNDS_RESELECT — every round starts with the (0, 0) neighbour selection on the handle's exchange
-    buffer (``nbr`` is only the table's first content), as ``LPVRounds(reselect=1)``."""
+    buffer (``nbr`` is only the table's first content), as ``LPVRounds(reselect=1)``.  ``log`` = capacity > 0:
+    the device log of the last ``capacity`` rounds (cmpc_lpv_rounds_log_enable; ``log_range()``, ``log()``),
+    with ``log_separation`` also each agent's nearest other agent; 0 (the default): off, every launch as before."""
+
+    _log_fn, _log_nx, _log_nu = "cmpc_lpv_rounds_log_", 9, 2
 
     def __init__(self, bp, x0, x_last, u_last, nbr, u_old=None, traj=None, rank=0, world=1, host_exchange=False,
-                 halt=True, reselect=False):
+                 halt=True, reselect=False, log=0, log_separation=False):
         self.bp, self.ctx = bp, bp.ctx
         x0 = L.f64(x0)
         n, N = x0.shape[0], bp.N
@@ -488,6 +576,7 @@ class LPVRoundsHandle:
                                                            ct.byref(self.dims), ct.byref(init), ct.byref(bp.opts),
                                                            ct.byref(h)))
         self.h = h
+        self._log_enable(log, log_separation)
 
     def step(self, rounds=1):
         """Runs up to `rounds` rounds; returns (rounds done, infeasible agents of the last one)."""
@@ -528,17 +617,21 @@ class LPVRoundsHandle:
             pass
 
 
-class DIRoundsHandle:
+class DIRoundsHandle(_HandleLog):
     """``DIRounds.step()`` (fused) through the C ABI's round handle (cmpc_di_rounds_*): the library owns the
     device state; no torch.  What a MATLAB (MEX) or C host drives for the synthetic family.  ``scen``: a
     ``scenarios.DIScenario``; ``rank`` / ``world``: this handle's contiguous shard, exchanged over the
     context's communicator or, with ``host_exchange``, by the caller between steps (get_traj / set_traj).
     ``reselect``: CMPC_ROUNDS_RESELECT, as ``DIRounds(reselect=1)``.  ``lpt``: CMPC_ROUNDS_LPT, the launch
     order from the previous round's iteration counts on the device (None: ``DIRounds``'s default rule).
-    ``history``: rounds of kkt / iters / status the device ring keeps (``history()``)."""
+    ``history``: rounds of kkt / iters / status the device ring keeps (``history()``).  ``log`` = capacity > 0:
+    the device log of the last ``capacity`` rounds (cmpc_di_rounds_log_enable; ``log_range()``, ``log()``), with
+    ``log_separation`` also each agent's nearest other agent; 0 (the default): off, every launch as before."""
+
+    _log_fn = "cmpc_di_rounds_log_"
 
     def __init__(self, scen, rank=0, world=1, ctx=None, tol=None, max_iter=None, fp32=False, host_exchange=False,
-                 reselect=False, lpt=None, history=1):
+                 reselect=False, lpt=None, history=1, log=0, log_separation=False):
         from .solver import FP32_TOL
 
         if scen.n_agents % world:
@@ -548,6 +641,7 @@ class DIRoundsHandle:
         sh = scen.shared
         self.B, self.n, self.N, self.nb = sl.stop - sl.start, scen.n_agents, scen.N, scen.nb
         self.nx, self.nu, self.nz = sh["nx"], sh["nu"], nz_of(sh)
+        self._log_nx, self._log_nu = self.nx, self.nu
         ric32 = (sh["nx"], sh["nu"], sh["mc"]) == (6, 3, 6)   # DIRounds's rule
         self.lpt = (self.N * sh["nu"] > 64 and (not fp32 or ric32)) if lpt is None else bool(lpt)
         flags = (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (L.CMPC_ROUNDS_RESELECT if reselect else 0) | \
@@ -565,6 +659,7 @@ class DIRoundsHandle:
         self.ctx.check(self.ctx.lib.cmpc_di_rounds_create(self.ctx.h, ct.byref(prm), ct.byref(w), ct.byref(self.dims),
                                                           ct.byref(init), ct.byref(opts), ct.byref(h)))
         self.h = h
+        self._log_enable(log, log_separation)
 
     def step(self, rounds=1):
         """Runs ``rounds`` rounds (one host synchronisation, at the end); returns the number done."""

@@ -135,6 +135,22 @@ def order_by_iters(iters):
     return np.argsort(-np.clip(np.asarray(iters, np.int64), 0, 65535), kind="stable").astype(np.int32)
 
 
+def log_row(z, nx, nu, ns, N, look_col):
+    """Host statement of a round's log rows (cmpc_round_log_dev, include/cmpc.h) from the round's ``z``
+    (batch, nz) in the reference layout, nz = (nx+ns)(N+1) + 2 nu N: what the reference appends per control step
+    to states.dat / u.dat / plan_dist.dat (config/base_class.py:64-99).  Returns (state, u, look_ahead):
+    state (batch, nx) = xPred[0], u (batch, nu) = uPred[0], look_ahead (batch,) =
+    xPred[-1, look_col] - xPred[0, look_col].  Copies, bit for bit; the look-ahead is one subtraction."""
+    z = np.asarray(z, np.float64)
+    nxe = nx + ns
+    if z.ndim != 2 or z.shape[1] != nxe * (N + 1) + 2 * nu * N or not (0 <= look_col < nx):
+        raise ValueError("z: (batch, (nx+ns)(N+1) + 2 nu N), 0 <= look_col < nx")
+    u0 = nxe * (N + 1)
+    with np.errstate(invalid="ignore"):
+        look = z[:, nxe * N + look_col] - z[:, look_col]
+    return z[:, :nx].copy(), z[:, u0:u0 + nu].copy(), look
+
+
 def make_di(n_agents, N, nb=2, dim=2, seed=SEED):
     rng = np.random.default_rng(seed)
     nx, nu = 2 * dim, dim

@@ -1,5 +1,5 @@
 // The C ABI's context object and the error helpers shared by the host-side translation units
-// (cmpc_api.hip, rounds_api.hip).  Not part of the public header: cmpc.h keeps cmpc_ctx opaque.
+// (cmpc_api.hip, rounds_api.hip, round_log.hip).  Not part of the public header: cmpc.h keeps cmpc_ctx opaque.
 #pragma once
 #include <string>
 

@@ -261,6 +261,25 @@ hipError_t nbr_select_launch(const NbrConst& c, const double* traj_all, int* nbr
 // index; tmp: batch x 8 bytes of device scratch.  One workgroup; nothing is launched for batch <= 0
 hipError_t order_launch(int batch, const int* iters, int* order, unsigned long long* tmp, hipStream_t s);
 
+// A round's log rows (round_log.hip): xPred[0], uPred[0], the look-ahead difference and the solver's per-agent
+// outputs out of the round's z / kkt / iters / status, one thread per output element.  A null destination is
+// skipped (its source is then not read); nothing is launched for batch <= 0 or when every destination is null
+struct LogConst {
+    int batch, nx, nu;
+    int nz;           // doubles per agent in z
+    int u_off;        // z index of uPred[0]: (nx + ns)(N + 1)
+    int hi, lo;       // z indices of the look-ahead's two terms: (nx + ns) N + look_col, look_col
+};
+struct LogPtrs {
+    const double* z;
+    const double* kkt;
+    const int* iters;
+    const int* status;
+    double *state, *u, *look, *kkt_out;
+    int *iters_out, *status_out;
+};
+hipError_t round_log_launch(const LogConst& c, const LogPtrs& p, hipStream_t s);
+
 // Synthetic double-integrator family (bench workload).
 
 struct DiPtrs {

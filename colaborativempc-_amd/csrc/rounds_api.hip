@@ -5,10 +5,29 @@
 //   [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's
 // communicator (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).
+// With the log on (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1]
+// into the handle's log ring, and an event pair brackets its solver call.
 // cmpc_di_rounds_* (further down) is the same handle for the synthetic double-integrator family.
+#include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "ctx.h"
+
+// The experiment log of a handle (cmpc_*_rounds_log_*): a device ring of `capacity` rounds, round r in row
+// r % capacity, and an event pair per row around the round's solver call.  A block of its own, made by
+// log_enable after create and freed by destroy; both handles share it.
+struct RoundLog {
+    int capacity = 0, flags = 0;
+    int first = 0;  // the log covers rounds [first, end): first = the handle's round count at enable
+    int end = 0;
+    cmpc_log_dims d{};
+    cmpc_nbr_dims sel{};  // CMPC_LOG_SEPARATION: nb = 1, window (0, 0)
+    char* mem = nullptr;
+    double *state = nullptr, *u = nullptr, *look = nullptr, *kkt = nullptr, *sep2 = nullptr;
+    int *iters = nullptr, *status = nullptr, *nearest = nullptr;
+    std::vector<hipEvent_t> ev;  // 2 x capacity: [2 row] before, [2 row + 1] after the solver call
+};
 
 struct cmpc_lpv_rounds {
     cmpc_ctx* ctx = nullptr;
@@ -18,6 +37,8 @@ struct cmpc_lpv_rounds {
     cmpc_lpv_rounds_dims d{};
     cmpc_opts opts{};
     int last_rows = 0;              // N + 1 in the first round, N afterwards (LPV_HP_N_main.py:115)
+    int rounds_done = 0;            // since create (the log's round numbers)
+    RoundLog* log = nullptr;        // cmpc_lpv_rounds_log_enable
     char* mem = nullptr;
     double *x0 = nullptr, *x_last = nullptr, *u_last = nullptr, *u_old = nullptr, *traj_all = nullptr,
            *traj_local = nullptr, *pose = nullptr, *x_agents = nullptr, *z = nullptr, *planes = nullptr,
@@ -37,6 +58,7 @@ struct cmpc_di_rounds {
     int row_slack[CMPC_MAX_MC]{}, row_sign[CMPC_MAX_MC]{};
     cmpc_mpc_weights w{};
     int rounds_done = 0;  // since create: round r writes row r % history of kkt / iters / status
+    RoundLog* log = nullptr;  // cmpc_di_rounds_log_enable
     char* mem = nullptr;
     double *A = nullptr, *B = nullptr, *x0 = nullptr, *u_prev = nullptr, *lane = nullptr, *traj_all = nullptr,
            *traj_local = nullptr, *qlin = nullptr, *C = nullptr, *h = nullptr, *z = nullptr, *kkt = nullptr;
@@ -47,6 +69,147 @@ namespace {
 
 size_t nz_lpv(int N) { return 12 * (size_t)(N + 1) + 4 * (size_t)N; }
 size_t nz_di(int nx, int nu, int N) { return (size_t)(nx + 3) * (N + 1) + 2 * (size_t)nu * N; }
+
+void log_free(RoundLog* lg) {
+    if (!lg) return;
+    for (hipEvent_t e : lg->ev) (void)hipEventDestroy(e);
+    (void)hipFree(lg->mem);
+    delete lg;
+}
+
+// d: the handle's log dimensions; sel: its population (nb, k0, k1 are set here); stale: a sharded host-exchange
+// handle, whose exchange buffer holds the other ranks' previous rows when a round ends
+int log_enable(cmpc_ctx* ctx, RoundLog** out, int capacity, int flags, const cmpc_log_dims& d, cmpc_nbr_dims sel,
+               bool stale, int round_now) {
+    if (*out) return fail(ctx, CMPC_ERR_ARG, "the log is already enabled");
+    if (capacity < 1) return fail(ctx, CMPC_ERR_ARG, "log capacity < 1");
+    if (flags & ~CMPC_LOG_SEPARATION) return fail(ctx, CMPC_ERR_ARG, "unknown log flag");
+    const bool sep = flags & CMPC_LOG_SEPARATION;
+    if (sep && sel.n_total < 2) return fail(ctx, CMPC_ERR_ARG, "CMPC_LOG_SEPARATION needs n_total >= 2");
+    if (sep && stale)
+        return fail(ctx, CMPC_ERR_ARG,
+                    "CMPC_LOG_SEPARATION on a sharded host-exchange handle: the other ranks' rows are stale when a "
+                    "round ends");
+    HIP_TRY(hipSetDevice(ctx->device));
+    auto* lg = new RoundLog();
+    lg->capacity = capacity;
+    lg->flags = flags;
+    lg->first = lg->end = round_now;
+    lg->d = d;
+    sel.nb = 1;
+    sel.k0 = sel.k1 = 0;
+    lg->sel = sel;
+    const size_t rows = (size_t)capacity * d.batch;
+    const size_t cnt8[] = {rows * d.nx, rows * d.nu, rows, rows, sep ? rows : 0};
+    const size_t cnt4[] = {rows, rows, sep ? rows : 0};
+    size_t bytes = 0;
+    for (size_t c : cnt8) bytes += (8 * c + 255) & ~size_t(255);
+    for (size_t c : cnt4) bytes += (4 * c + 255) & ~size_t(255);
+    if (hipMalloc(&lg->mem, bytes) != hipSuccess) {
+        lg->mem = nullptr;
+        log_free(lg);
+        return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the log ring failed");
+    }
+    size_t off = 0;
+    auto take = [&](size_t b) {
+        char* p = lg->mem + off;
+        off += (b + 255) & ~size_t(255);
+        return p;
+    };
+    double** dp[] = {&lg->state, &lg->u, &lg->look, &lg->kkt, &lg->sep2};
+    for (int i = 0; i < 5; ++i) *dp[i] = reinterpret_cast<double*>(take(8 * cnt8[i]));
+    int** ip[] = {&lg->iters, &lg->status, &lg->nearest};
+    for (int i = 0; i < 3; ++i) *ip[i] = reinterpret_cast<int*>(take(4 * cnt4[i]));
+    if (!sep) {
+        lg->sep2 = nullptr;
+        lg->nearest = nullptr;
+    }
+    hipError_t e = hipMemsetAsync(lg->mem, 0, bytes, ctx->stream);
+    for (int i = 0; e == hipSuccess && i < 2 * capacity; ++i) {
+        hipEvent_t ev;
+        if ((e = hipEventCreate(&ev)) == hipSuccess) lg->ev.push_back(ev);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        log_free(lg);
+        return hip_fail(ctx, e, "log_enable");
+    }
+    *out = lg;
+    return CMPC_OK;
+}
+
+// the event before (which = 0) / after (1) round r's solver call; nothing waits on it during the step
+hipError_t log_mark(RoundLog* lg, int r, int which, hipStream_t s) {
+    return lg ? hipEventRecord(lg->ev[2 * (size_t)(r % lg->capacity) + which], s) : hipSuccess;
+}
+
+// round r's solver call failed after its first event was recorded: row r % capacity no longer times round
+// r - capacity, which leaves the log
+void log_abandon(RoundLog* lg, int r) {
+    if (lg) lg->first = std::max(lg->first, std::min(lg->end, r - lg->capacity + 1));
+}
+
+// round r's rows, stream-ordered after its exchange
+int log_round(cmpc_ctx* ctx, RoundLog* lg, int r, const double* z, const double* kkt, const int* iters,
+              const int* status, const double* traj_all, hipStream_t s) {
+    const size_t row = (size_t)(r % lg->capacity) * lg->d.batch;
+    const cmpc_log_row dst{lg->state + row * lg->d.nx, lg->u + row * lg->d.nu, lg->look + row,
+                           lg->kkt + row, lg->iters + row, lg->status + row};
+    int rc = cmpc_round_log_dev(ctx, &lg->d, z, kkt, iters, status, &dst, s);
+    if (rc == CMPC_OK && (lg->flags & CMPC_LOG_SEPARATION))
+        rc = cmpc_nbr_select_dev(ctx, &lg->sel, traj_all, lg->nearest + row, lg->sep2 + row, s);
+    if (rc != CMPC_OK) return rc;
+    if (r != lg->end) lg->first = r;  // a round in between went unlogged (its exchange failed): the log restarts here
+    lg->end = r + 1;
+    return CMPC_OK;
+}
+
+int log_range(cmpc_ctx* ctx, const RoundLog* lg, int* first_round, int* count) {
+    if (!lg) return fail(ctx, CMPC_ERR_ARG, "the log is not enabled (log_enable)");
+    const int lo = std::max(lg->first, lg->end - lg->capacity);
+    if (first_round) *first_round = lo;
+    if (count) *count = lg->end - lo;
+    return CMPC_OK;
+}
+
+int log_read(cmpc_ctx* ctx, const RoundLog* lg, int first_round, int count, const cmpc_rounds_log* o) {
+    if (!lg) return fail(ctx, CMPC_ERR_ARG, "the log is not enabled (log_enable)");
+    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
+    if (!(lg->flags & CMPC_LOG_SEPARATION) && (o->sep2 || o->nearest))
+        return fail(ctx, CMPC_ERR_ARG, "sep2 / nearest: the log was enabled without CMPC_LOG_SEPARATION");
+    if (first_round < 0 || count < 0 || (long long)first_round + count > lg->end)
+        return fail(ctx, CMPC_ERR_ARG, "log: a round that has not run yet");
+    if (count > 0 && first_round < std::max(lg->first, lg->end - lg->capacity))
+        return fail(ctx, CMPC_ERR_ARG, "log: a round from before log_enable, or one the ring has already overwritten");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the ring's rows of the range: [r0, r0 + n1), then [0, count - n1) after the wrap
+    const size_t B = lg->d.batch, r0 = (size_t)(first_round % lg->capacity),
+                 n1 = std::min((size_t)count, lg->capacity - r0), n2 = count - n1;
+    auto pull = [&](void* dst, const void* src, size_t row_bytes) {
+        if (!dst || !count || !row_bytes) return hipSuccess;
+        hipError_t e = hipMemcpyAsync(dst, (const char*)src + r0 * row_bytes, n1 * row_bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && n2)
+            e = hipMemcpyAsync((char*)dst + n1 * row_bytes, src, n2 * row_bytes, hipMemcpyDeviceToHost, s);
+        return e;
+    };
+    HIP_TRY(pull(o->state, lg->state, 8 * B * lg->d.nx));
+    HIP_TRY(pull(o->u, lg->u, 8 * B * lg->d.nu));
+    HIP_TRY(pull(o->look_ahead, lg->look, 8 * B));
+    HIP_TRY(pull(o->kkt, lg->kkt, 8 * B));
+    HIP_TRY(pull(o->iters, lg->iters, 4 * B));
+    HIP_TRY(pull(o->status, lg->status, 4 * B));
+    HIP_TRY(pull(o->sep2, lg->sep2, 8 * B));
+    HIP_TRY(pull(o->nearest, lg->nearest, 4 * B));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; o->solve_ms && i < count; ++i) {
+        const size_t row = (size_t)((first_round + i) % lg->capacity);
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, lg->ev[2 * row], lg->ev[2 * row + 1]));
+        o->solve_ms[i] = ms;
+    }
+    return CMPC_OK;
+}
 
 }  // namespace
 
@@ -170,7 +333,12 @@ int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* 
         const cmpc_lpv_dims ld{h->d.batch, h->d.N, nb, h->last_rows};
         const cmpc_lpv_data din{h->x0, h->x_last, h->u_last, h->u_old, nb ? h->x_agents : nullptr, h->pose};
         const cmpc_lpv_out dout{h->z, nb ? h->planes : nullptr, h->kkt, h->iters, h->status};
-        if ((rc = cmpc_solve_lpv_batch_dev(ctx, &h->prm, &h->track, &ld, &din, &dout, &h->opts, s)) != CMPC_OK) return rc;
+        HIP_TRY(log_mark(h->log, h->rounds_done, 0, s));
+        if ((rc = cmpc_solve_lpv_batch_dev(ctx, &h->prm, &h->track, &ld, &din, &dout, &h->opts, s)) != CMPC_OK) {
+            log_abandon(h->log, h->rounds_done);
+            return rc;
+        }
+        HIP_TRY(log_mark(h->log, h->rounds_done, 1, s));
         HIP_TRY(hipMemsetAsync(h->infeasible, 0, sizeof(int), s));
         if (h->last_rows == h->d.N + 1) {
             // first round: Last_xPredicted goes from N + 1 rows per agent to N dense ones.  The advance
@@ -197,6 +365,11 @@ int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* 
         // rank that broke alone would leave the others waiting in the next round's all-gather).
         // The host exchange runs one round per step: its caller combines the counts it returns.
         if (sharded && !host_x && (rc = cmpc_comm_sum_i32(ctx, h->infeasible, 1, s)) != CMPC_OK) return rc;
+        // the log's rows of this round (a round that halts the loop below has run, and is logged)
+        if (h->log && (rc = log_round(ctx, h->log, h->rounds_done, h->z, h->kkt, h->iters, h->status, h->traj_all,
+                                      s)) != CMPC_OK)
+            return rc;
+        ++h->rounds_done;
         ++done;
         if (halt || r + 1 == rounds) {  // the reference stops the experiment at an infeasible agent
             HIP_TRY(hipMemcpyAsync(&bad, h->infeasible, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -254,9 +427,27 @@ int cmpc_lpv_rounds_destroy(cmpc_lpv_rounds* h) {
     if (!h) return CMPC_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
+    log_free(h->log);
     (void)hipFree(h->mem);
     delete h;
     return CMPC_OK;
+}
+
+int cmpc_lpv_rounds_log_enable(cmpc_lpv_rounds* h, int capacity, int flags) {
+    if (!h) return CMPC_ERR_ARG;
+    const cmpc_lpv_rounds_dims& d = h->d;
+    const cmpc_log_dims ld{d.batch, 9, 2, 3, d.N, 6};
+    const cmpc_nbr_dims sd{d.batch, d.N, 1, d.self_offset, d.n_total, 0, 0};
+    return log_enable(h->ctx, &h->log, capacity, flags, ld, sd,
+                      (d.flags & CMPC_ROUNDS_HOST_EXCHANGE) && d.batch != d.n_total, h->rounds_done);
+}
+
+int cmpc_lpv_rounds_log_range(cmpc_lpv_rounds* h, int* first_round, int* count) {
+    return h ? log_range(h->ctx, h->log, first_round, count) : CMPC_ERR_ARG;
+}
+
+int cmpc_lpv_rounds_log_read(cmpc_lpv_rounds* h, int first_round, int count, const cmpc_rounds_log* o) {
+    return h ? log_read(h->ctx, h->log, first_round, count, o) : CMPC_ERR_ARG;
 }
 
 // ---- the synthetic double-integrator family (cmpc_di_rounds_*): what cmpc.rounds.DIRounds.step() chains ----
@@ -384,9 +575,20 @@ int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done) {
             (rc = cmpc_nbr_select_dev(ctx, &sd, h->traj_all, h->nbr, nullptr, s)) != CMPC_OK)
             break;
         h->opts.order = (lpt && h->rounds_done > 0) ? h->order : nullptr;
-        if ((rc = cmpc_di_round_dev(ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w, &din, &dout,
-                                    &h->opts, h->traj_local, s)) != CMPC_OK)
+        hipError_t ev = log_mark(h->log, h->rounds_done, 0, s);
+        if (ev != hipSuccess) {
+            rc = hip_fail(ctx, ev, "cmpc_di_rounds_step: log event");
             break;
+        }
+        if ((rc = cmpc_di_round_dev(ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w, &din, &dout,
+                                    &h->opts, h->traj_local, s)) != CMPC_OK) {
+            log_abandon(h->log, h->rounds_done);
+            break;
+        }
+        if ((ev = log_mark(h->log, h->rounds_done, 1, s)) != hipSuccess) {
+            rc = hip_fail(ctx, ev, "cmpc_di_rounds_step: log event");
+            break;
+        }
         // the next round's launch order, stream-ordered after this solve
         if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) break;
         ++h->rounds_done;  // the round's outputs exist from here on, whatever the exchange returns
@@ -397,6 +599,10 @@ int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done) {
         } else if (!host_x) {
             rc = cmpc_allgather_trajectories(ctx, h->traj_local, h->traj_all, row * B, s);
         }
+        // the log's rows of this round, from the history-ring row the solver wrote
+        if (h->log && rc == CMPC_OK)
+            rc = log_round(ctx, h->log, h->rounds_done - 1, h->z, h->kkt + slot, h->iters + slot, h->status + slot,
+                           h->traj_all, s);
     }
     // one host synchronisation, also after an error: the rounds already queued have then finished
     const hipError_t e = hipStreamSynchronize(s);
@@ -472,9 +678,27 @@ int cmpc_di_rounds_destroy(cmpc_di_rounds* h) {
     if (!h) return CMPC_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
+    log_free(h->log);
     (void)hipFree(h->mem);
     delete h;
     return CMPC_OK;
+}
+
+int cmpc_di_rounds_log_enable(cmpc_di_rounds* h, int capacity, int flags) {
+    if (!h) return CMPC_ERR_ARG;
+    const cmpc_di_rounds_dims& d = h->d;
+    const cmpc_log_dims ld{d.batch, h->md.nx, h->md.nu, 3, d.N, 0};
+    const cmpc_nbr_dims sd{d.batch, d.N, 1, d.self_offset, d.n_total, 0, 0};
+    return log_enable(h->ctx, &h->log, capacity, flags, ld, sd,
+                      (d.flags & CMPC_ROUNDS_HOST_EXCHANGE) && d.batch != d.n_total, h->rounds_done);
+}
+
+int cmpc_di_rounds_log_range(cmpc_di_rounds* h, int* first_round, int* count) {
+    return h ? log_range(h->ctx, h->log, first_round, count) : CMPC_ERR_ARG;
+}
+
+int cmpc_di_rounds_log_read(cmpc_di_rounds* h, int first_round, int count, const cmpc_rounds_log* o) {
+    return h ? log_read(h->ctx, h->log, first_round, count, o) : CMPC_ERR_ARG;
 }
 
 }  // extern "C"

@@ -8,6 +8,15 @@
  *   [z, status, kkt, iters, x0, u_prev, nbr] = cmpc_di('rounds_read', h)      the latest round
  *   [kkt, iters, status] = cmpc_di('rounds_history', h, first, count)         B x count each, rounds counted
  *                                                    from create (0-based); S.history rounds are kept
+ *   cmpc_di('rounds_log_enable', h, capacity [, flags])   cmpc_di_rounds_log_enable: a device log of the last
+ *                                                    `capacity` rounds from here on; flags 1 = CMPC_LOG_SEPARATION
+ *   L = cmpc_di('rounds_log', h [, first, count])    cmpc_di_rounds_log_read: rounds first .. first+count-1 (0-based,
+ *                                                    counted from create; default: all the ring holds) as a struct —
+ *                                                    first (scalar), state nx x B x count (x_0 of the round),
+ *                                                    u nu x B x count (u_0), look_ahead, kkt, iters, status
+ *                                                    B x count, solve_ms count x 1 (the whole batch's solver launch,
+ *                                                    ms), and with CMPC_LOG_SEPARATION sep2, nearest B x count
+ *                                                    (0-based global index of the nearest other agent)
  *   T = cmpc_di('rounds_get_traj', h)                this rank's predicted positions (host exchange)
  *   cmpc_di('rounds_set_traj', h, T)                 the gathered exchange buffer (host exchange)
  *   cmpc_di('rounds_destroy', h)
@@ -39,6 +48,7 @@
 static cmpc_ctx* g_ctx = NULL;
 static cmpc_di_rounds* g_h[MAX_HANDLES];
 static int g_hN[MAX_HANDLES], g_hB[MAX_HANDLES], g_hnb[MAX_HANDLES], g_hT[MAX_HANDLES], g_hdim[MAX_HANDLES];
+static int g_hlog[MAX_HANDLES]; /* CMPC_LOG_* flags of rounds_log_enable */
 
 static void cleanup(void) {
     for (int i = 0; i < MAX_HANDLES; ++i)
@@ -179,6 +189,7 @@ static void rounds_create(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
     g_hnb[slot] = nb;
     g_hT[slot] = n_total;
     g_hdim[slot] = prm.dim;
+    g_hlog[slot] = 0;
     plhs[0] = mxCreateDoubleMatrix(1, 1, mxREAL);
     mxGetPr(plhs[0])[0] = slot + 1;
 }
@@ -258,6 +269,62 @@ static void rounds_history(int nlhs, mxArray* plhs[], int nrhs, const mxArray* p
     if (nlhs > 2) plhs[2] = ST;
 }
 
+static void rounds_log_enable(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    (void)nlhs;
+    (void)plhs;
+    if (nrhs != 3 && nrhs != 4)
+        mexErrMsgIdAndTxt("cmpc:di:args", "usage: cmpc_di('rounds_log_enable', h, capacity [, flags])");
+    const int h = handle_of(prhs[1]);
+    const int flags = nrhs > 3 ? (int)mxGetScalar(prhs[3]) : 0;
+    check(cmpc_di_rounds_log_enable(g_h[h], (int)mxGetScalar(prhs[2]), flags), "cmpc_di_rounds_log_enable");
+    g_hlog[h] = flags;
+}
+
+static void rounds_log(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    (void)nlhs;
+    if (nrhs != 2 && nrhs != 4) mexErrMsgIdAndTxt("cmpc:di:args", "usage: L = cmpc_di('rounds_log', h [, first, count])");
+    const int h = handle_of(prhs[1]);
+    const int B = g_hB[h], nx = 2 * g_hdim[h], nu = g_hdim[h], sep = g_hlog[h] & CMPC_LOG_SEPARATION;
+    int first = 0, count = 0;
+    if (nrhs == 2) {
+        check(cmpc_di_rounds_log_range(g_h[h], &first, &count), "cmpc_di_rounds_log_range");
+    } else {
+        first = (int)mxGetScalar(prhs[2]);
+        count = (int)mxGetScalar(prhs[3]);
+    }
+    if (first < 0 || count < 0) mexErrMsgIdAndTxt("cmpc:di:args", "first and count must be >= 0");
+    const size_t n = (size_t)B * count;
+    const mwSize ds[3] = {(mwSize)nx, (mwSize)B, (mwSize)count}, du[3] = {(mwSize)nu, (mwSize)B, (mwSize)count};
+    mxArray* XS = mxCreateNumericArray(3, ds, mxDOUBLE_CLASS, mxREAL);
+    mxArray* US = mxCreateNumericArray(3, du, mxDOUBLE_CLASS, mxREAL);
+    mxArray* LA = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* KK = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* IT = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* ST = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* S2 = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* NR = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* MS = mxCreateDoubleMatrix(count, 1, mxREAL);
+    int* ibuf = (int*)mxCalloc(3 * (n ? n : 1), sizeof(int));
+    int *iters = ibuf, *status = ibuf + (n ? n : 1), *nearest = status + (n ? n : 1);
+    const cmpc_rounds_log o = {mxGetPr(XS), mxGetPr(US), mxGetPr(LA), mxGetPr(KK), iters, status,
+                               sep ? mxGetPr(S2) : NULL, sep ? nearest : NULL, mxGetPr(MS)};
+    const int rc = cmpc_di_rounds_log_read(g_h[h], first, count, &o);
+    if (rc == CMPC_OK) {
+        widen(IT, iters, n);
+        widen(ST, status, n);
+        if (sep) widen(NR, nearest, n);
+    }
+    mxFree(ibuf);
+    check(rc, "cmpc_di_rounds_log_read");
+    const char* names[] = {"first", "state", "u", "look_ahead", "kkt", "iters", "status", "solve_ms", "sep2", "nearest"};
+    mxArray* L = mxCreateStructMatrix(1, 1, sep ? 10 : 8, names);
+    mxArray* F = mxCreateDoubleMatrix(1, 1, mxREAL);
+    mxGetPr(F)[0] = first;
+    mxArray* vals[] = {F, XS, US, LA, KK, IT, ST, MS, S2, NR};
+    for (int i = 0; i < (sep ? 10 : 8); ++i) mxSetField(L, 0, names[i], vals[i]);
+    plhs[0] = L;
+}
+
 static void rounds_traj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int set) {
     (void)nlhs;
     if (nrhs != (set ? 3 : 2)) mexErrMsgIdAndTxt("cmpc:di:args", "usage: rounds_get_traj(h) / rounds_set_traj(h, T)");
@@ -280,7 +347,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char cmd[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], cmd, sizeof cmd) != 0)
         mexErrMsgIdAndTxt("cmpc:di:args", "usage: cmpc_di('rounds_create' | 'rounds_step' | 'rounds_read' | "
-                                          "'rounds_history' | 'rounds_get_traj' | 'rounds_set_traj' | "
+                                          "'rounds_history' | 'rounds_log_enable' | 'rounds_log' | 'rounds_get_traj' | 'rounds_set_traj' | "
                                           "'rounds_destroy' | 'comm_id' | 'comm_init', ...)");
     if (!strcmp(cmd, "rounds_create")) {
         rounds_create(nlhs, plhs, nrhs, prhs);
@@ -290,6 +357,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         rounds_read(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_history")) {
         rounds_history(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rounds_log_enable")) {
+        rounds_log_enable(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rounds_log")) {
+        rounds_log(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_get_traj") || !strcmp(cmd, "rounds_set_traj")) {
         rounds_traj(nlhs, plhs, nrhs, prhs, cmd[7] == 's');
     } else if (!strcmp(cmd, "rounds_destroy")) {

@@ -11,6 +11,14 @@
  *   h = cmpc_lpv('rounds_create', P, D, S)           cmpc_lpv_rounds_create: device-resident rounds
  *   [done, infeasible] = cmpc_lpv('rounds_step', h, k)   k rounds (gather, solve, advance, exchange)
  *   [z, status, kkt, iters, x0, planes] = cmpc_lpv('rounds_read', h)
+ *   cmpc_lpv('rounds_log_enable', h, capacity [, flags])   cmpc_lpv_rounds_log_enable: a device log of the last
+ *       `capacity` rounds from here on (the rows of the reference's csv/<id>/ files); flags 1 = CMPC_LOG_SEPARATION
+ *   L = cmpc_lpv('rounds_log', h [, first, count])   cmpc_lpv_rounds_log_read: rounds first .. first+count-1 (0-based,
+ *       counted from create; default: all the ring holds) as a struct — first (scalar), state 9 x B x count
+ *       (xPred[0]: states.dat), u 2 x B x count (uPred[0]: u.dat), look_ahead B x count (xPred[-1, 6] - xPred[0, 6]:
+ *       plan_dist.dat), kkt, iters, status B x count, solve_ms count x 1 (the whole batch's solver launch in ms, the
+ *       same for every agent; / 1e3 for time.dat), and with CMPC_LOG_SEPARATION sep2, nearest B x count (0-based
+ *       global index of the nearest other agent)
  *   T = cmpc_lpv('rounds_get_traj', h)               this rank's predicted X, Y (host exchange)
  *   cmpc_lpv('rounds_set_traj', h, T)                the gathered exchange buffer (host exchange)
  *   cmpc_lpv('rounds_destroy', h)
@@ -45,6 +53,7 @@
 static cmpc_ctx* g_ctx = NULL;
 static cmpc_lpv_rounds* g_h[MAX_HANDLES];
 static int g_hN[MAX_HANDLES], g_hB[MAX_HANDLES], g_hnb[MAX_HANDLES], g_hT[MAX_HANDLES];
+static int g_hlog[MAX_HANDLES]; /* CMPC_LOG_* flags of rounds_log_enable */
 
 static void cleanup(void) {
     for (int i = 0; i < MAX_HANDLES; ++i)
@@ -275,6 +284,7 @@ static void rounds_create(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
     g_hB[slot] = b.B;
     g_hnb[slot] = nb;
     g_hT[slot] = n_total;
+    g_hlog[slot] = 0;
     plhs[0] = mxCreateDoubleMatrix(1, 1, mxREAL);
     mxGetPr(plhs[0])[0] = slot + 1;
 }
@@ -324,6 +334,62 @@ static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     if (nlhs > 5) plhs[5] = PL;
 }
 
+static void rounds_log_enable(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    (void)nlhs;
+    (void)plhs;
+    if (nrhs != 3 && nrhs != 4)
+        mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('rounds_log_enable', h, capacity [, flags])");
+    const int h = handle_of(prhs[1]);
+    const int flags = nrhs > 3 ? (int)mxGetScalar(prhs[3]) : 0;
+    check(cmpc_lpv_rounds_log_enable(g_h[h], (int)mxGetScalar(prhs[2]), flags), "cmpc_lpv_rounds_log_enable");
+    g_hlog[h] = flags;
+}
+
+static void rounds_log(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    (void)nlhs;
+    if (nrhs != 2 && nrhs != 4) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: L = cmpc_lpv('rounds_log', h [, first, count])");
+    const int h = handle_of(prhs[1]);
+    const int B = g_hB[h], sep = g_hlog[h] & CMPC_LOG_SEPARATION;
+    int first = 0, count = 0;
+    if (nrhs == 2) {
+        check(cmpc_lpv_rounds_log_range(g_h[h], &first, &count), "cmpc_lpv_rounds_log_range");
+    } else {
+        first = (int)mxGetScalar(prhs[2]);
+        count = (int)mxGetScalar(prhs[3]);
+    }
+    if (first < 0 || count < 0) mexErrMsgIdAndTxt("cmpc:lpv:args", "first and count must be >= 0");
+    const size_t n = (size_t)B * count;
+    mxArray* XS = dmat3(9, B, count);
+    mxArray* US = dmat3(2, B, count);
+    mxArray* LA = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* KK = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* IT = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* ST = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* S2 = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* NR = mxCreateDoubleMatrix(B, count, mxREAL);
+    mxArray* MS = mxCreateDoubleMatrix(count, 1, mxREAL);
+    int* ibuf = (int*)mxCalloc(3 * (n ? n : 1), sizeof(int));
+    int *iters = ibuf, *status = ibuf + (n ? n : 1), *nearest = status + (n ? n : 1);
+    const cmpc_rounds_log o = {mxGetPr(XS), mxGetPr(US), mxGetPr(LA), mxGetPr(KK), iters, status,
+                               sep ? mxGetPr(S2) : NULL, sep ? nearest : NULL, mxGetPr(MS)};
+    const int rc = cmpc_lpv_rounds_log_read(g_h[h], first, count, &o);
+    if (rc == CMPC_OK)
+        for (size_t i = 0; i < n; ++i) {
+            mxGetPr(IT)[i] = iters[i];
+            mxGetPr(ST)[i] = status[i];
+            if (sep) mxGetPr(NR)[i] = nearest[i];
+        }
+    mxFree(ibuf);
+    check(rc, "cmpc_lpv_rounds_log_read");
+    const char* names[] = {"first", "state", "u", "look_ahead", "kkt", "iters", "status", "solve_ms", "sep2", "nearest"};
+    mxArray* L = mxCreateStructMatrix(1, 1, sep ? 10 : 8, names);
+    mxArray* F = mxCreateDoubleMatrix(1, 1, mxREAL);
+    mxGetPr(F)[0] = first;
+    mxArray* vals[] = {F, XS, US, LA, KK, IT, ST, MS, S2, NR};
+    for (int i = 0; i < (sep ? 10 : 8); ++i) mxSetField(L, 0, names[i], vals[i]);
+    plhs[0] = L;
+}
+
 static void rounds_traj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int set) {
     (void)nlhs;
     if (nrhs != (set ? 3 : 2)) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: rounds_get_traj(h) / rounds_set_traj(h, T)");
@@ -345,6 +411,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char cmd[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], cmd, sizeof cmd) != 0)
         mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('solve' | 'rounds_create' | 'rounds_step' | 'rounds_read' | "
+                                           "'rounds_log_enable' | 'rounds_log' | "
                                            "'rounds_get_traj' | 'rounds_set_traj' | 'rounds_destroy' | 'comm_id' | "
                                            "'comm_init', ...)");
     if (!strcmp(cmd, "solve")) {
@@ -355,6 +422,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         rounds_step(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_read")) {
         rounds_read(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rounds_log_enable")) {
+        rounds_log_enable(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rounds_log")) {
+        rounds_log(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_get_traj") || !strcmp(cmd, "rounds_set_traj")) {
         rounds_traj(nlhs, plhs, nrhs, prhs, cmd[7] == 's');
     } else if (!strcmp(cmd, "rounds_destroy")) {

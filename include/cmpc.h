@@ -47,7 +47,8 @@ extern "C" {
                                 6: cmpc_plan_info waves_per_agent / polish_lds_bytes / polish_max_active;
                                 still 6 (additions only: no struct grew, no entry point changed):
                                 cmpc_nbr_select_dev, CMPC_ROUNDS_RESELECT; cmpc_order_by_iters_dev,
-                                cmpc_di_rounds_*, CMPC_ROUNDS_LPT */
+                                cmpc_di_rounds_*, CMPC_ROUNDS_LPT; cmpc_round_log_dev,
+                                cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, CMPC_LOG_SEPARATION */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -565,6 +566,80 @@ int cmpc_di_rounds_get_traj(cmpc_di_rounds* h, double* traj_local);
 int cmpc_di_rounds_set_traj(cmpc_di_rounds* h, const double* traj_all);
 /* Destroy every handle of a context before cmpc_destroy(ctx). */
 int cmpc_di_rounds_destroy(cmpc_di_rounds* h);
+
+/* ------------------------------------------------------------------------
+ * The experiment log of a round, on the device.  The reference's run ends in csv/<id>/{states,u,plan_dist,
+ * time}.dat (config/base_class.py:64-99): per control step xPred[0], uPred[0], xPred[-1, 6] - xPred[0, 6] and the
+ * solve time.  The first three are entries of the round's z.
+ *
+ * cmpc_round_log_dev: DEVICE pointers, stream-ordered, no host synchronisation.  One launch copies, for every
+ * agent b of one round (z in the reference layout, xi_k = [x_k (nx) | s_k (ns)], nz = (nx+ns)(N+1) + 2 nu N):
+ *   row->state[b, 0..nx)  <- z[b, 0 .. nx)                                      xPred[0]
+ *   row->u[b, 0..nu)      <- z[b, (nx+ns)(N+1) .. +nu)                          uPred[0]
+ *   row->look_ahead[b]    <- z[b, (nx+ns)N + look_col] - z[b, look_col]         one subtraction
+ *   row->kkt / iters / status[b] <- kkt / iters / status[b]                     the round's solver outputs
+ * bit for bit (a NaN z — an agent the builder flagged — gives NaN rows).  Any destination may be NULL: that part
+ * is skipped.  The pointers are one round's rows: a caller that keeps a ring adds the row offset on the host, so
+ * the launch takes plain pointers (graph-capturable like the others).  One thread per output element,
+ * consecutive threads on consecutive addresses of a destination.
+ * CMPC_ERR_ARG: NULL dims, z or row; a NULL kkt / iters / status whose destination is set; batch < 0; N < 1;
+ * nx < 1 or nx > CMPC_MAX_NX; nu < 1 or nu > CMPC_MAX_NU; ns < 0 or ns > CMPC_MAX_NS; look_col outside [0, nx).
+ * batch == 0: CMPC_OK without a launch.  cmpc.scenarios.log_row is its numpy statement.
+ * ---------------------------------------------------------------------- */
+typedef struct { int batch, nx, nu, ns, N; int look_col; } cmpc_log_dims;   /* look_col: state column of the look-ahead */
+typedef struct {            /* DEVICE pointers to ONE round's rows; any may be NULL (that part is skipped) */
+    double *state;          /* batch x nx : z[b, 0 .. nx)                       = xPred[0]               */
+    double *u;              /* batch x nu : z[b, (nx+ns)(N+1) .. +nu)           = uPred[0]               */
+    double *look_ahead;     /* batch      : z[b, (nx+ns)N + look_col] - z[b, look_col]  (one subtraction) */
+    double *kkt; int *iters, *status;     /* batch: copies of the round's solver outputs                 */
+} cmpc_log_row;
+int cmpc_round_log_dev(cmpc_ctx* ctx, const cmpc_log_dims* dims, const double* z /* batch x nz */, const double* kkt,
+                       const int* iters, const int* status, const cmpc_log_row* row, void* hip_stream);
+
+/* The log on the round handles: cmpc_lpv_rounds_step(h, 100, ...) / cmpc_di_rounds_step(h, 100, ...) leave every
+ * round's states, inputs, look-ahead, solver outputs and solve time readable afterwards, with no host
+ * synchronisation or copy per round.
+ *
+ * _log_enable (after create; the handle's structs and ABI are unchanged) allocates a device ring of `capacity`
+ * rounds and 2 x capacity events, freed by _destroy.  Rounds are counted from create (both handles); the log
+ * covers rounds from the handle's round count at the moment of the call, round r in row r mod capacity.  With
+ * the log on, a round ends — after its exchange — with cmpc_round_log_dev on the round's z and its kkt / iters /
+ * status (the DI handle: the history-ring row the solver wrote):
+ *   LPV: nx, nu, ns = 9, 2, 3, look_col = 6 (s: the reference's plan_dist);
+ *   DI:  nx = 2 dim, nu = dim, ns = 3, look_col = 0 (the predicted advance along the road).
+ * A round that halts the LPV loop is logged (it ran); a round whose solver call returns an API error is not.
+ * solve_ms: an event pair on the context's stream around the round's solver call (cmpc_solve_lpv_batch_dev /
+ * cmpc_di_round_dev) and nothing else; nothing waits on the events during the step, _log_read resolves them
+ * after its own synchronise.  It is the WHOLE BATCH's launch time — the same for every agent of the rank, not a
+ * per-agent solve time (the reference times each agent's OSQP call).  Milliseconds.
+ * CMPC_LOG_SEPARATION: after the exchange, cmpc_nbr_select_dev with nb = 1, window (0, 0), on the exchange
+ * buffer, straight into the ring: `nearest` = each local agent's nearest other agent at stage 0 (global index)
+ * and `sep2` the squared distance — cmpc.scenarios.select_neighbours(traj_all, 1, (0, 0), rows = the local
+ * agents, return_dist2 = True) on the buffer as that round's exchange left it (stage 0 = every agent's logged
+ * xPred[0] position).  Needs n_total >= 2, and not a sharded CMPC_ROUNDS_HOST_EXCHANGE handle (its exchange
+ * happens after the step: the other ranks' rows would be stale).
+ * With the log off every launch and every output of a step is what it was.
+ *
+ * _log_range: the rounds the ring holds now, [*first_round, *first_round + *count); (k, 0) before the first
+ * logged round, k the handle's round count at enable.
+ * _log_read: rounds [first_round, first_round + count) into HOST arrays with leading dimension count (any may be
+ * NULL).  Synchronises the host.
+ * CMPC_ERR_ARG: a NULL handle; _log_enable twice, capacity < 1, an unknown flag, CMPC_LOG_SEPARATION with
+ * n_total < 2 or on a sharded host-exchange handle; _log_range / _log_read without _log_enable; a NULL output
+ * struct; first_round < 0, count < 0; a round that has not run, ran before _log_enable, or has been overwritten
+ * (count == 0 inside the rounds run so far: CMPC_OK); sep2 / nearest without CMPC_LOG_SEPARATION. */
+#define CMPC_LOG_SEPARATION 1
+typedef struct {            /* HOST pointers, any may be NULL; leading dimension = count */
+    double *state, *u, *look_ahead, *kkt; int *iters, *status;   /* count x batch [x nx | x nu] */
+    double *sep2; int *nearest;                                  /* count x batch (CMPC_LOG_SEPARATION) */
+    double *solve_ms;                                            /* count: the batch's solver launch, ms */
+} cmpc_rounds_log;
+int cmpc_lpv_rounds_log_enable(cmpc_lpv_rounds* h, int capacity, int flags);
+int cmpc_lpv_rounds_log_range(cmpc_lpv_rounds* h, int* first_round, int* count);
+int cmpc_lpv_rounds_log_read(cmpc_lpv_rounds* h, int first_round, int count, const cmpc_rounds_log* host_out);
+int cmpc_di_rounds_log_enable(cmpc_di_rounds* h, int capacity, int flags);
+int cmpc_di_rounds_log_range(cmpc_di_rounds* h, int* first_round, int* count);
+int cmpc_di_rounds_log_read(cmpc_di_rounds* h, int first_round, int count, const cmpc_rounds_log* host_out);
 
 
 /* ------------------------------------------------------------------------
