@@ -160,20 +160,98 @@ def log_round_dev(z, nx, nu, ns, N, look_col, row=None, kkt=None, iters=None, st
     return row
 
 
-class _HandleLog:
-    """The device log of a round handle (cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, include/cmpc.h); the
-    handle class sets ``_log_fn`` (the entry points' common prefix) and ``_log_nx`` / ``_log_nu``."""
+def _di_params(p):
+    """cmpc_di_params of a scenario's ``params``."""
+    return L.cmpc_di_params(int(p["dim"]), *(float(p[k]) for k in ("v_ref", "q_v", "q_lane", "hw", "min_vel", "max_vel",
+                                                                     "min_dist", "wq")))
 
-    def _log_enable(self, capacity, separation):
-        self.log_separation = bool(separation)
-        if capacity or separation:
-            fn = getattr(self.ctx.lib, self._log_fn + "enable")
-            self.ctx.check(fn(self.h, int(capacity), L.CMPC_LOG_SEPARATION if separation else 0))
+
+def _di_opts(tol, max_iter, fp32):
+    """The synthetic family's cmpc_opts: fp32 selects CMPC_FLAG_FP32 and, without ``tol``, FP32_TOL."""
+    from .solver import FP32_TOL
+
+    return L.opts(tol or (FP32_TOL if fp32 else None), max_iter, L.CMPC_FLAG_FP32 if fp32 else 0)
+
+
+def _lpt_default(sh, N, fp32):
+    """Whether the agents are launched longest-first, by last round's IPM iterations (cmpc_opts.order), when the
+    caller does not say: on where the stage-wise Riccati solver runs (many agents per SIMD there, so the launch
+    otherwise ends with whichever slow agents happened to start last; the condensed kernels have one agent per
+    SIMD and ignore the order).  The fp32 lane kernel packs its wavefronts in that order, but at cfg5 all of its
+    256 wavefronts run at once (one per CU), so its launch still ends with the slowest agent (measured 91.9 ->
+    99.8 ms): off where fp32 runs on it, i.e. on dimensions without the Riccati kernel's fp32 instantiation
+    (6, 3, 6)."""
+    ric32 = (sh["nx"], sh["nu"], sh["mc"]) == (6, 3, 6)
+    return N * sh["nu"] > 64 and (not fp32 or ric32)
+
+
+class _TorchRounds:
+    """What the torch-driven ``DIRounds`` / ``LPVRounds`` share; they set ``torch``, ``dev``, ``ctx``, the shard
+    (``B``, ``off``, ``nb``, ``world``, ``group``, ``comm``), ``traj_all`` / ``traj_local`` / ``nbr`` and
+    ``reselect_window``."""
+
+    def _stream(self):
+        return ct.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def exchange(self):
+        exchange_positions(self.traj_all, self.traj_local, self.world, self.group, self.comm)
+
+    def select_neighbours(self, window=None):
+        """One selection into ``self.nbr``, in place: this rank's agents against the exchange buffer as it
+        stands (``select_neighbours_dev``; ``window`` defaults to ``reselect_window``)."""
+        select_neighbours_dev(self.traj_all, self.nb, self.B, self.off, self.reselect_window if window is None
+                              else window, out=self.nbr, ctx=self.ctx)
+
+
+class _RoundsHandle:
+    """What the two round-handle wrappers share (cmpc_lpv_rounds_* / cmpc_di_rounds_*, include/cmpc.h): the
+    handle's lifetime, the host exchange and the device log.  A wrapper sets ``_fn`` (the entry points' common
+    prefix), ``ctx``, ``B``, ``n``, ``N`` and ``nx`` / ``nu`` (the widths of the log's state and input rows)."""
+
+    def _call(self, name, *args):
+        self.ctx.check(getattr(self.ctx.lib, self._fn + name)(self.h, *args))
+
+    @staticmethod
+    def _flags(host_exchange=False, halt=True, reselect=False, lpt=False):
+        return (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (0 if halt else L.CMPC_ROUNDS_NO_HALT) | \
+            (L.CMPC_ROUNDS_RESELECT if reselect else 0) | (L.CMPC_ROUNDS_LPT if lpt else 0)
+
+    def _create(self, args, log, log_separation):
+        """<prefix>create(ctx, *args, &h), then the log (``log`` = capacity)."""
+        h = ct.c_void_p()
+        create = getattr(self.ctx.lib, self._fn + "create")
+        self.ctx.check(create(self.ctx.h, *[ct.byref(a) for a in args], ct.byref(h)))
+        self.h = h
+        self.log_separation = bool(log_separation)
+        if log or log_separation:
+            self._call("log_enable", int(log), L.CMPC_LOG_SEPARATION if log_separation else 0)
+
+    def get_traj(self):
+        t = np.zeros((self.B, self.N + 1, 2))
+        self._call("get_traj", L.dptr(t))
+        return t
+
+    def set_traj(self, traj_all):
+        t = L.f64(traj_all)
+        if t.shape != (self.n, self.N + 1, 2):
+            raise ValueError("traj_all: (n_total, N+1, 2)")
+        self._call("set_traj", L.dptr(t))
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.ctx.lib, self._fn + "destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def log_range(self):
         """(first, count): the rounds the log ring holds now, counted from create."""
         first, count = ct.c_int(), ct.c_int()
-        self.ctx.check(getattr(self.ctx.lib, self._log_fn + "range")(self.h, ct.byref(first), ct.byref(count)))
+        self._call("log_range", ct.byref(first), ct.byref(count))
         return first.value, count.value
 
     def log(self, first=None, count=None):
@@ -188,7 +266,7 @@ class _HandleLog:
             first = lo if first is None else first
             count = lo + n - first if count is None else count
         c = max(int(count), 0)
-        r = dict(state=np.zeros((c, self.B, self._log_nx)), u=np.zeros((c, self.B, self._log_nu)),
+        r = dict(state=np.zeros((c, self.B, self.nx)), u=np.zeros((c, self.B, self.nu)),
                  look_ahead=np.zeros((c, self.B)), kkt=np.zeros((c, self.B)), iters=np.zeros((c, self.B), np.int32),
                  status=np.zeros((c, self.B), np.int32), solve_ms=np.zeros(c))
         if self.log_separation:
@@ -196,11 +274,11 @@ class _HandleLog:
         o = L.cmpc_rounds_log(L.dptr(r["state"]), L.dptr(r["u"]), L.dptr(r["look_ahead"]), L.dptr(r["kkt"]),
                               L.iptr(r["iters"]), L.iptr(r["status"]), L.dptr(r.get("sep2")), L.iptr(r.get("nearest")),
                               L.dptr(r["solve_ms"]))
-        self.ctx.check(getattr(self.ctx.lib, self._log_fn + "read")(self.h, int(first), int(count), ct.byref(o)))
+        self._call("log_read", int(first), int(count), ct.byref(o))
         return r
 
 
-class DIRounds:
+class DIRounds(_TorchRounds):
     """Device-resident consensus rounds of the synthetic double-integrator agents (module docstring).
 
     ``reselect`` = r > 0: the neighbour table ``self.nbr`` is re-selected on the device, in place, at the
@@ -247,25 +325,12 @@ class DIRounds:
         self.kkt = torch.empty(self.B, dtype=torch.float64, device=self.dev)
         self.iters = torch.empty(self.B, dtype=torch.int32, device=self.dev)
         self.status = torch.empty(self.B, dtype=torch.int32, device=self.dev)
-        p = scen.params
-        self.dprm = L.cmpc_di_params(int(p["dim"]), *(float(p[k]) for k in ("v_ref", "q_v", "q_lane", "hw",
-                                                                              "min_vel", "max_vel", "min_dist",
-                                                                              "wq")))
+        self.dprm = _di_params(scen.params)
         self.ddims = L.cmpc_di_dims(self.B, self.N, self.nb, self.off)
         self.mdims = _dims(sh, self.B)
         self.w, self._wkeep = _weights(sh)
-        from .solver import FP32_TOL
-
-        self.opts = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, L.CMPC_FLAG_FP32 if fp32 else 0)
-        # lpt: launch the Riccati solver's agents longest-first, by last round's IPM iterations
-        # (cmpc_opts.order; many agents per SIMD there, so the launch otherwise ends with whichever
-        # slow agents happened to start last).  Default: on where the stage-wise solver runs (the
-        # condensed kernels have one agent per SIMD and ignore the order).  The fp32 lane kernel packs
-        # its wavefronts in that order, but at cfg5 all of its 256 wavefronts run at once (one per CU),
-        # so its launch still ends with the slowest agent (measured 91.9 -> 99.8 ms): off where fp32
-        # runs on it, i.e. on dimensions without the Riccati kernel's fp32 instantiation (6, 3, 6).
-        ric32 = (sh["nx"], sh["nu"], sh["mc"]) == (6, 3, 6)
-        self.lpt = (self.N * sh["nu"] > 64 and (not fp32 or ric32)) if lpt is None else bool(lpt)
+        self.opts = _di_opts(tol, max_iter, fp32)
+        self.lpt = _lpt_default(sh, self.N, fp32) if lpt is None else bool(lpt)   # cmpc_opts.order
         self._order = None
         self.data = L.cmpc_mpc_data(*[_tptr(t) for t in (self.A, self.Bm, self.x0, self.u_prev, self.qlin,
                                                           self.C, self.h)])
@@ -282,9 +347,6 @@ class DIRounds:
                 raise ValueError(f"{name}: need a contiguous ({self.B},) {dt} tensor on {self.dev}")
         self.kkt, self.iters, self.status = kkt, iters, status
         self.out = L.cmpc_mpc_out(_tptr(self.z), _tptr(kkt), _tptr(iters), _tptr(status))
-
-    def _stream(self):
-        return ct.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def build(self):
         lib = self.ctx.lib
@@ -335,15 +397,6 @@ class DIRounds:
                                                         _tptr(self.z), _tptr(self.x0), _tptr(self.u_prev),
                                                         _tptr(self.traj_local), self._stream()))
 
-    def exchange(self):
-        exchange_positions(self.traj_all, self.traj_local, self.world, self.group, self.comm)
-
-    def select_neighbours(self, window=None):
-        """One selection into ``self.nbr``, in place: this rank's agents against the exchange buffer as it
-        stands (``select_neighbours_dev``; ``window`` defaults to ``reselect_window``)."""
-        select_neighbours_dev(self.traj_all, self.nb, self.B, self.off, self.reselect_window if window is None
-                              else window, out=self.nbr, ctx=self.ctx)
-
     def step(self, timer=None):
         """One consensus round.  `timer` (start, stop) events bracket the solve launch (with
         `fused`, the launch that builds and solves)."""
@@ -373,7 +426,7 @@ class DIRounds:
         return p
 
 
-class LPVRounds:
+class LPVRounds(_TorchRounds):
     """Device-resident consensus rounds of the reference's LPV agents (LPV_HP_N_main.py:96-117):
     per round gather (neighbour and own positions from the exchange buffer) -> build + solve
     (cmpc_solve_lpv_batch_dev: scheduling, planes, weights, rows, the QP) -> advance (x0 <-
@@ -441,15 +494,6 @@ class LPVRounds:
         # agents of the latest round the reference calls infeasible (status not in {1, 2, -2})
         self.n_infeasible = torch.zeros(1, dtype=torch.int32, device=self.dev)
 
-    def _stream(self):
-        return ct.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def select_neighbours(self, window=None):
-        """One selection into ``self.nbr``, in place: this rank's agents against the exchange buffer as it
-        stands (``select_neighbours_dev``; ``window`` defaults to ``reselect_window``)."""
-        select_neighbours_dev(self.traj_all, self.nb, self.B, self.off, self.reselect_window if window is None
-                              else window, out=self.nbr, ctx=self.ctx)
-
     def gather(self):
         lib = self.ctx.lib
         self.ctx.check(lib.cmpc_lpv_gather_dev(self.ctx.h, ct.byref(self.rdims), _tptr(self.nbr), _tptr(self.traj_all),
@@ -483,9 +527,6 @@ class LPVRounds:
                                                          _tptr(self.status), _tptr(self.n_infeasible),
                                                          self._stream()))
         self.last_rows = self.N   # x_old = xPred[1:] from now on (LPV_HP_N_main.py:115)
-
-    def exchange(self):
-        exchange_positions(self.traj_all, self.traj_local, self.world, self.group, self.comm)
 
     def step(self, timer=None, halt=True):
         """One consensus round.  `timer` (start, stop) events bracket the build + solve launch.
@@ -541,7 +582,7 @@ class InfeasibleRound(RuntimeError):
         self.count = count
 
 
-class LPVRoundsHandle(_HandleLog):
+class LPVRoundsHandle(_RoundsHandle):
     """The same rounds through the C ABI's round handle (cmpc_lpv_rounds_*): the library owns the
     device state; no torch.  What a MATLAB (MEX) or C host drives.  Arguments as LPVRounds;
     ``host_exchange``: the caller exchanges positions between steps (get_traj / set_traj).  ``reselect``:
@@ -550,7 +591,7 @@ class LPVRoundsHandle(_HandleLog):
     the device log of the last ``capacity`` rounds (cmpc_lpv_rounds_log_enable; ``log_range()``, ``log()``),
     with ``log_separation`` also each agent's nearest other agent; 0 (the default): off, every launch as before."""
 
-    _log_fn, _log_nx, _log_nu = "cmpc_lpv_rounds_log_", 9, 2
+    _fn, nx, nu = "cmpc_lpv_rounds_", 9, 2
 
     def __init__(self, bp, x0, x_last, u_last, nbr, u_old=None, traj=None, rank=0, world=1, host_exchange=False,
                  halt=True, reselect=False, log=0, log_separation=False):
@@ -563,25 +604,18 @@ class LPVRoundsHandle(_HandleLog):
         B = n // world
         sl = slice(rank * B, (rank + 1) * B)
         self.N, self.nb, self.B, self.n = N, nbr.shape[1], B, n
-        flags = (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (0 if halt else L.CMPC_ROUNDS_NO_HALT) | \
-            (L.CMPC_ROUNDS_RESELECT if reselect else 0)
-        self.dims = L.cmpc_lpv_rounds_dims(n, B, rank * B, N, self.nb, flags)
+        self.dims = L.cmpc_lpv_rounds_dims(n, B, rank * B, N, self.nb, self._flags(host_exchange, halt, reselect))
         keep = [L.f64(x0[sl]), L.f64(np.asarray(x_last)[sl]), L.f64(np.asarray(u_last)[sl]),
                 None if u_old is None else L.f64(np.asarray(u_old)[sl]), L.i32(nbr[sl]),
                 None if traj is None else L.f64(traj)]
         init = L.cmpc_lpv_rounds_init(L.dptr(keep[0]), L.dptr(keep[1]), L.dptr(keep[2]), L.dptr(keep[3]),
                                       L.iptr(keep[4]), L.dptr(keep[5]))
-        h = ct.c_void_p()
-        self.ctx.check(self.ctx.lib.cmpc_lpv_rounds_create(self.ctx.h, ct.byref(bp.prm), ct.byref(bp.track),
-                                                           ct.byref(self.dims), ct.byref(init), ct.byref(bp.opts),
-                                                           ct.byref(h)))
-        self.h = h
-        self._log_enable(log, log_separation)
+        self._create((bp.prm, bp.track, self.dims, init, bp.opts), log, log_separation)
 
     def step(self, rounds=1):
         """Runs up to `rounds` rounds; returns (rounds done, infeasible agents of the last one)."""
         done, bad = ct.c_int(), ct.c_int()
-        self.ctx.check(self.ctx.lib.cmpc_lpv_rounds_step(self.h, int(rounds), ct.byref(done), ct.byref(bad)))
+        self._call("step", int(rounds), ct.byref(done), ct.byref(bad))
         return done.value, bad.value
 
     def read(self):
@@ -591,33 +625,11 @@ class LPVRoundsHandle(_HandleLog):
                  planes=np.zeros((self.B, self.N, 3, self.nb)))
         o = L.cmpc_lpv_rounds_out(L.dptr(r["z"]), L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]),
                                   L.dptr(r["x0"]), L.dptr(r["planes"]) if self.nb else None)
-        self.ctx.check(self.ctx.lib.cmpc_lpv_rounds_read(self.h, ct.byref(o)))
+        self._call("read", ct.byref(o))
         return r
 
-    def get_traj(self):
-        t = np.zeros((self.B, self.N + 1, 2))
-        self.ctx.check(self.ctx.lib.cmpc_lpv_rounds_get_traj(self.h, L.dptr(t)))
-        return t
 
-    def set_traj(self, traj_all):
-        t = L.f64(traj_all)
-        if t.shape != (self.n, self.N + 1, 2):
-            raise ValueError("traj_all: (n_total, N+1, 2)")
-        self.ctx.check(self.ctx.lib.cmpc_lpv_rounds_set_traj(self.h, L.dptr(t)))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.cmpc_lpv_rounds_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DIRoundsHandle(_HandleLog):
+class DIRoundsHandle(_RoundsHandle):
     """``DIRounds.step()`` (fused) through the C ABI's round handle (cmpc_di_rounds_*): the library owns the
     device state; no torch.  What a MATLAB (MEX) or C host drives for the synthetic family.  ``scen``: a
     ``scenarios.DIScenario``; ``rank`` / ``world``: this handle's contiguous shard, exchanged over the
@@ -628,12 +640,10 @@ class DIRoundsHandle(_HandleLog):
     the device log of the last ``capacity`` rounds (cmpc_di_rounds_log_enable; ``log_range()``, ``log()``), with
     ``log_separation`` also each agent's nearest other agent; 0 (the default): off, every launch as before."""
 
-    _log_fn = "cmpc_di_rounds_log_"
+    _fn = "cmpc_di_rounds_"
 
     def __init__(self, scen, rank=0, world=1, ctx=None, tol=None, max_iter=None, fp32=False, host_exchange=False,
                  reselect=False, lpt=None, history=1, log=0, log_separation=False):
-        from .solver import FP32_TOL
-
         if scen.n_agents % world:
             raise ValueError("n_agents must be divisible by the number of ranks")
         self.ctx = ctx or L.default_context(0)
@@ -641,30 +651,19 @@ class DIRoundsHandle(_HandleLog):
         sh = scen.shared
         self.B, self.n, self.N, self.nb = sl.stop - sl.start, scen.n_agents, scen.N, scen.nb
         self.nx, self.nu, self.nz = sh["nx"], sh["nu"], nz_of(sh)
-        self._log_nx, self._log_nu = self.nx, self.nu
-        ric32 = (sh["nx"], sh["nu"], sh["mc"]) == (6, 3, 6)   # DIRounds's rule
-        self.lpt = (self.N * sh["nu"] > 64 and (not fp32 or ric32)) if lpt is None else bool(lpt)
-        flags = (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (L.CMPC_ROUNDS_RESELECT if reselect else 0) | \
-            (L.CMPC_ROUNDS_LPT if self.lpt else 0)
+        self.lpt = _lpt_default(sh, self.N, fp32) if lpt is None else bool(lpt)
+        flags = self._flags(host_exchange, reselect=reselect, lpt=self.lpt)
         self.dims = L.cmpc_di_rounds_dims(self.n, self.B, sl.start, self.N, self.nb, flags, int(history))
-        p = scen.params
-        prm = L.cmpc_di_params(int(p["dim"]), *(float(p[k]) for k in ("v_ref", "q_v", "q_lane", "hw", "min_vel",
-                                                                        "max_vel", "min_dist", "wq")))
         w, wkeep = _weights(sh)
         keep = [L.f64(scen.A[sl]), L.f64(scen.B[sl]), L.f64(scen.x0[sl]), L.f64(scen.u_prev[sl]), L.f64(scen.lane[sl]),
                 L.i32(scen.nbr[sl]), L.f64(scen.traj)]
         init = L.cmpc_di_rounds_init(*[L.dptr(a) for a in keep[:5]], L.iptr(keep[5]), L.dptr(keep[6]))
-        opts = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, L.CMPC_FLAG_FP32 if fp32 else 0)
-        h = ct.c_void_p()
-        self.ctx.check(self.ctx.lib.cmpc_di_rounds_create(self.ctx.h, ct.byref(prm), ct.byref(w), ct.byref(self.dims),
-                                                          ct.byref(init), ct.byref(opts), ct.byref(h)))
-        self.h = h
-        self._log_enable(log, log_separation)
+        self._create((_di_params(scen.params), w, self.dims, init, _di_opts(tol, max_iter, fp32)), log, log_separation)
 
     def step(self, rounds=1):
         """Runs ``rounds`` rounds (one host synchronisation, at the end); returns the number done."""
         done = ct.c_int()
-        self.ctx.check(self.ctx.lib.cmpc_di_rounds_step(self.h, int(rounds), ct.byref(done)))
+        self._call("step", int(rounds), ct.byref(done))
         return done.value
 
     def read(self):
@@ -674,7 +673,7 @@ class DIRoundsHandle(_HandleLog):
                  nbr=np.zeros((self.B, self.nb), np.int32))
         o = L.cmpc_di_rounds_out(L.dptr(r["z"]), L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]),
                                  L.dptr(r["x0"]), L.dptr(r["u_prev"]), L.iptr(r["nbr"]) if self.nb else None)
-        self.ctx.check(self.ctx.lib.cmpc_di_rounds_read(self.h, ct.byref(o)))
+        self._call("read", ct.byref(o))
         return r
 
     def history(self, first, count):
@@ -683,28 +682,5 @@ class DIRoundsHandle(_HandleLog):
         count = int(count)
         r = dict(kkt=np.zeros((max(count, 0), self.B)), iters=np.zeros((max(count, 0), self.B), np.int32),
                  status=np.zeros((max(count, 0), self.B), np.int32))
-        self.ctx.check(self.ctx.lib.cmpc_di_rounds_history(self.h, int(first), count, L.dptr(r["kkt"]),
-                                                           L.iptr(r["iters"]), L.iptr(r["status"])))
+        self._call("history", int(first), count, L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]))
         return r
-
-    def get_traj(self):
-        t = np.zeros((self.B, self.N + 1, 2))
-        self.ctx.check(self.ctx.lib.cmpc_di_rounds_get_traj(self.h, L.dptr(t)))
-        return t
-
-    def set_traj(self, traj_all):
-        t = L.f64(traj_all)
-        if t.shape != (self.n, self.N + 1, 2):
-            raise ValueError("traj_all: (n_total, N+1, 2)")
-        self.ctx.check(self.ctx.lib.cmpc_di_rounds_set_traj(self.h, L.dptr(t)))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.cmpc_di_rounds_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

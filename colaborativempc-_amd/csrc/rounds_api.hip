@@ -1,22 +1,57 @@
-// Consensus rounds behind a handle (include/cmpc.h, cmpc_lpv_rounds_*): the device-resident loop of
-// LPV_HP_N_main.py:96-117 for hosts that own no device memory (MATLAB through the MEX gateway, C).
-// The handle owns this rank's agent state and the node-global exchange buffer in one device
-// allocation; a round chains the C-ABI device entry points on the context's stream:
-//   [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
-// where the exchange is a device copy (one rank), the RCCL all-gather of the context's
-// communicator (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).
-// With the log on (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1]
-// into the handle's log ring, and an event pair brackets its solver call.
-// cmpc_di_rounds_* (further down) is the same handle for the synthetic double-integrator family.
+// Consensus rounds behind a handle (include/cmpc.h, cmpc_lpv_rounds_* and cmpc_di_rounds_*): the device-resident
+// loop of LPV_HP_N_main.py:96-117 for hosts that own no device memory (MATLAB through the MEX gateways, C).
+// A handle owns this rank's agent state and the node-global exchange buffer in one device allocation; a round
+// chains the C-ABI device entry points on the context's stream:
+//   LPV: [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
+//   DI:  [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
+// where the exchange is a device copy (one rank), the RCCL all-gather of the context's communicator
+// (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).  With the log on
+// (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1] into the
+// handle's log ring, and an event pair brackets its solver call.
+//
+// What the two families share lives once, in RoundsCore and the functions on it: the create checks, the device
+// block, the re-selection, the exchange, get / set_traj, destroy and the log.  The two step loops stay apart
+// (their middles differ), and so do their error paths: the LPV step returns at once, without a host
+// synchronisation, and counts a round only after its exchange and log rows; the DI step counts a round as soon
+// as its solver call and launch order are queued (its outputs exist whatever the exchange returns), leaves the
+// loop at the first error and synchronises the host once before it returns the error.
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "ctx.h"
 
+namespace {
+
+// One sub-array of a device block: where its address goes and its size.
+struct Part {
+    void** p;
+    size_t bytes;
+    template <class T>
+    Part(T*& ptr, size_t count) : p(reinterpret_cast<void**>(&ptr)), bytes(sizeof(T) * count) {}
+    size_t padded() const { return (bytes + 255) & ~size_t(255); }
+};
+
+// One hipMalloc for all `parts`, each 256-byte aligned, in list order (an empty part gets nullptr).  Sizes and
+// addresses come from the same list.  Returns the block's bytes, 0 when the allocation failed (*mem = nullptr).
+size_t device_block(char** mem, std::initializer_list<Part> parts) {
+    size_t bytes = 0, off = 0;
+    for (const Part& a : parts) bytes += a.padded();
+    if (hipMalloc(mem, bytes) != hipSuccess) {
+        *mem = nullptr;
+        return 0;
+    }
+    for (const Part& a : parts) {
+        *a.p = a.bytes ? *mem + off : nullptr;
+        off += a.padded();
+    }
+    return bytes;
+}
+
 // The experiment log of a handle (cmpc_*_rounds_log_*): a device ring of `capacity` rounds, round r in row
 // r % capacity, and an event pair per row around the round's solver call.  A block of its own, made by
-// log_enable after create and freed by destroy; both handles share it.
+// log_enable after create and freed by destroy.
 struct RoundLog {
     int capacity = 0, flags = 0;
     int first = 0;  // the log covers rounds [first, end): first = the handle's round count at enable
@@ -29,46 +64,143 @@ struct RoundLog {
     std::vector<hipEvent_t> ev;  // 2 x capacity: [2 row] before, [2 row + 1] after the solver call
 };
 
-struct cmpc_lpv_rounds {
+}  // namespace
+
+// What both handles are made of.
+struct RoundsCore {
     cmpc_ctx* ctx = nullptr;
+    cmpc_lpv_rounds_dims d{};  // n_total, batch, self_offset, N, nb, flags: what both families' dims begin with
+    cmpc_opts opts{};
+    int rounds_done = 0;       // since create (the log's round numbers)
+    RoundLog* log = nullptr;   // cmpc_*_rounds_log_enable
+    char* mem = nullptr;       // the device block of everything below and of the family's own arrays
+    double *traj_all = nullptr, *traj_local = nullptr;
+    int* nbr = nullptr;
+
+    bool sharded() const { return d.batch != d.n_total; }
+    bool host_exchange() const { return d.flags & CMPC_ROUNDS_HOST_EXCHANGE; }
+    size_t traj_row() const { return 2 * (size_t)(d.N + 1); }  // doubles of one agent's predicted positions
+};
+
+struct cmpc_lpv_rounds : RoundsCore {
     cmpc_lpv_params prm{};
     double seg[4][CMPC_MAX_SEG]{};  // copy of the track table: s0, len, curv, half_width
     cmpc_track track{};
-    cmpc_lpv_rounds_dims d{};
-    cmpc_opts opts{};
     int last_rows = 0;              // N + 1 in the first round, N afterwards (LPV_HP_N_main.py:115)
-    int rounds_done = 0;            // since create (the log's round numbers)
-    RoundLog* log = nullptr;        // cmpc_lpv_rounds_log_enable
-    char* mem = nullptr;
-    double *x0 = nullptr, *x_last = nullptr, *u_last = nullptr, *u_old = nullptr, *traj_all = nullptr,
-           *traj_local = nullptr, *pose = nullptr, *x_agents = nullptr, *z = nullptr, *planes = nullptr,
-           *kkt = nullptr, *x_dense = nullptr;
-    int *nbr = nullptr, *iters = nullptr, *status = nullptr, *infeasible = nullptr;
+    double *x0 = nullptr, *x_last = nullptr, *u_last = nullptr, *u_old = nullptr, *pose = nullptr,
+           *x_agents = nullptr, *z = nullptr, *planes = nullptr, *kkt = nullptr, *x_dense = nullptr;
+    int *iters = nullptr, *status = nullptr, *infeasible = nullptr;
 };
 
-struct cmpc_di_rounds {
-    cmpc_ctx* ctx = nullptr;
+struct cmpc_di_rounds : RoundsCore {
     cmpc_di_params prm{};
-    cmpc_di_rounds_dims d{};  // history >= 1
+    int history = 1;  // round r writes row r % history of kkt / iters / status
     cmpc_mpc_dims md{};
-    cmpc_opts opts{};
     // copy of the batch-shared weights (cmpc_mpc_weights holds host pointers)
     double Q[CMPC_MAX_NX * CMPC_MAX_NX]{}, R[CMPC_MAX_NU * CMPC_MAX_NU]{}, dR[CMPC_MAX_NU * CMPC_MAX_NU]{},
         Qs[CMPC_MAX_NS]{}, u_ub[CMPC_MAX_NU]{}, u_lb[CMPC_MAX_NU]{};
     int row_slack[CMPC_MAX_MC]{}, row_sign[CMPC_MAX_MC]{};
     cmpc_mpc_weights w{};
-    int rounds_done = 0;  // since create: round r writes row r % history of kkt / iters / status
-    RoundLog* log = nullptr;  // cmpc_di_rounds_log_enable
-    char* mem = nullptr;
-    double *A = nullptr, *B = nullptr, *x0 = nullptr, *u_prev = nullptr, *lane = nullptr, *traj_all = nullptr,
-           *traj_local = nullptr, *qlin = nullptr, *C = nullptr, *h = nullptr, *z = nullptr, *kkt = nullptr;
-    int *nbr = nullptr, *iters = nullptr, *status = nullptr, *order = nullptr;
+    double *A = nullptr, *B = nullptr, *x0 = nullptr, *u_prev = nullptr, *lane = nullptr, *qlin = nullptr,
+           *C = nullptr, *h = nullptr, *z = nullptr, *kkt = nullptr;
+    int *iters = nullptr, *status = nullptr, *order = nullptr;
 };
 
 namespace {
 
 size_t nz_lpv(int N) { return 12 * (size_t)(N + 1) + 4 * (size_t)N; }
 size_t nz_di(int nx, int nu, int N) { return (size_t)(nx + 3) * (N + 1) + 2 * (size_t)nu * N; }
+
+// ---- create ----
+
+// The create checks both families share (`nbr`: init->nbr); CMPC_OK, or CMPC_ERR_ARG with the message set.
+int check_create(cmpc_ctx* ctx, const cmpc_lpv_rounds_dims& d, int known_flags, const int* nbr, const cmpc_opts* opts) {
+    if (d.N < 1 || d.nb < 0 || 4 + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
+        d.self_offset + d.batch > d.n_total)
+        return fail(ctx, CMPC_ERR_ARG, "bad rounds dimensions (1 <= batch, self_offset + batch <= n_total, nb <= 12)");
+    if (d.flags & ~known_flags) return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
+    if ((d.flags & CMPC_ROUNDS_RESELECT) && d.nb >= d.n_total)
+        return fail(ctx, CMPC_ERR_ARG, "CMPC_ROUNDS_RESELECT selects nb < n_total neighbours");
+    if (d.nb > 0 && !nbr) return fail(ctx, CMPC_ERR_ARG, "null initial state");
+    if (d.batch != d.n_total && !(d.flags & CMPC_ROUNDS_HOST_EXCHANGE) &&
+        (!ctx->comm || (long)ctx->nranks * d.batch != d.n_total || ctx->rank * d.batch != d.self_offset))
+        return fail(ctx, CMPC_ERR_ARG,
+                    "a sharded population exchanges over the context's communicator (cmpc_comm_init: equal "
+                    "contiguous shards in rank order) or the host's (CMPC_ROUNDS_HOST_EXCHANGE)");
+    for (int i = 0; i < d.batch * d.nb; ++i)
+        if (nbr[i] < 0 || nbr[i] >= d.n_total) return fail(ctx, CMPC_ERR_ARG, "neighbour index out of range");
+    if (opts && (opts->flags & ~CMPC_FLAG_ALL)) return fail(ctx, CMPC_ERR_ARG, "unknown option flag");
+    return CMPC_OK;
+}
+
+void core_init(RoundsCore* h, cmpc_ctx* ctx, const cmpc_lpv_rounds_dims& d, const cmpc_opts* opts) {
+    h->ctx = ctx;
+    h->d = d;
+    if (opts) h->opts = *opts;
+    h->opts.stamps = nullptr;
+    h->opts.order = nullptr;
+}
+
+hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+}
+
+// The end of both creates, after the family's uploads (`e`: their result): this rank's rows of the exchange
+// buffer -> traj_local (an agent that is not advanced keeps its initial ones), and the host synchronisation.
+hipError_t finish_uploads(RoundsCore* h, hipError_t e) {
+    hipStream_t s = h->ctx->stream;
+    const size_t own = 8 * h->traj_row() * h->d.batch;
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h->traj_local, h->traj_all + h->traj_row() * h->d.self_offset, own, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
+
+// ---- the parts of a round that both step loops call ----
+
+// CMPC_ROUNDS_RESELECT: this round's neighbours are the nb nearest in the exchange buffer as it stands
+int reselect(RoundsCore* h, hipStream_t s) {
+    if (!(h->d.flags & CMPC_ROUNDS_RESELECT) || h->d.nb == 0) return CMPC_OK;
+    const cmpc_nbr_dims sd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->d.n_total, 0, 0};
+    return cmpc_nbr_select_dev(h->ctx, &sd, h->traj_all, h->nbr, nullptr, s);
+}
+
+// traj_local -> every rank's traj_all; with the host's exchange (sharded) nothing: the host does it between steps
+int exchange(RoundsCore* h, hipStream_t s) {
+    const size_t count = h->traj_row() * h->d.batch;
+    if (h->sharded())
+        return h->host_exchange() ? CMPC_OK : cmpc_allgather_trajectories(h->ctx, h->traj_local, h->traj_all, count, s);
+    const hipError_t e = hipMemcpyAsync(h->traj_all, h->traj_local, 8 * count, hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? CMPC_OK : hip_fail(h->ctx, e, "rounds step: exchange");
+}
+
+// what both steps check before their loops
+int check_step(const RoundsCore* h, int rounds) {
+    if (rounds < 0) return fail(h->ctx, CMPC_ERR_ARG, "negative round count");
+    if (h->host_exchange() && h->sharded() && rounds > 1)
+        return fail(h->ctx, CMPC_ERR_ARG, "host exchange: one round per step (exchange between steps)");
+    return CMPC_OK;
+}
+
+// ---- get_traj / set_traj / destroy ----
+
+int copy_traj(RoundsCore* h, void* dst, const void* src, size_t agents, hipMemcpyKind kind) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!dst || !src) return fail(ctx, CMPC_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(dst, src, 8 * h->traj_row() * agents, kind, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return CMPC_OK;
+}
+
+int get_traj(RoundsCore* h, double* traj_local) {
+    return h ? copy_traj(h, traj_local, h->traj_local, h->d.batch, hipMemcpyDeviceToHost) : CMPC_ERR_ARG;
+}
+
+int set_traj(RoundsCore* h, const double* traj_all) {
+    return h ? copy_traj(h, h->traj_all, traj_all, h->d.n_total, hipMemcpyHostToDevice) : CMPC_ERR_ARG;
+}
 
 void log_free(RoundLog* lg) {
     if (!lg) return;
@@ -77,16 +209,30 @@ void log_free(RoundLog* lg) {
     delete lg;
 }
 
-// d: the handle's log dimensions; sel: its population (nb, k0, k1 are set here); stale: a sharded host-exchange
-// handle, whose exchange buffer holds the other ranks' previous rows when a round ends
-int log_enable(cmpc_ctx* ctx, RoundLog** out, int capacity, int flags, const cmpc_log_dims& d, cmpc_nbr_dims sel,
-               bool stale, int round_now) {
-    if (*out) return fail(ctx, CMPC_ERR_ARG, "the log is already enabled");
+template <class Handle>
+int destroy(Handle* h) {
+    if (!h) return CMPC_OK;
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    log_free(h->log);
+    (void)hipFree(h->mem);
+    delete h;
+    return CMPC_OK;
+}
+
+// ---- the log ----
+
+// nx, nu, look_col: the family's state and input widths and its look-ahead column
+int log_enable(RoundsCore* h, int capacity, int flags, int nx, int nu, int look_col) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    const cmpc_lpv_rounds_dims& d = h->d;
+    if (h->log) return fail(ctx, CMPC_ERR_ARG, "the log is already enabled");
     if (capacity < 1) return fail(ctx, CMPC_ERR_ARG, "log capacity < 1");
     if (flags & ~CMPC_LOG_SEPARATION) return fail(ctx, CMPC_ERR_ARG, "unknown log flag");
     const bool sep = flags & CMPC_LOG_SEPARATION;
-    if (sep && sel.n_total < 2) return fail(ctx, CMPC_ERR_ARG, "CMPC_LOG_SEPARATION needs n_total >= 2");
-    if (sep && stale)
+    if (sep && d.n_total < 2) return fail(ctx, CMPC_ERR_ARG, "CMPC_LOG_SEPARATION needs n_total >= 2");
+    if (sep && h->host_exchange() && h->sharded())
         return fail(ctx, CMPC_ERR_ARG,
                     "CMPC_LOG_SEPARATION on a sharded host-exchange handle: the other ranks' rows are stale when a "
                     "round ends");
@@ -94,35 +240,16 @@ int log_enable(cmpc_ctx* ctx, RoundLog** out, int capacity, int flags, const cmp
     auto* lg = new RoundLog();
     lg->capacity = capacity;
     lg->flags = flags;
-    lg->first = lg->end = round_now;
-    lg->d = d;
-    sel.nb = 1;
-    sel.k0 = sel.k1 = 0;
-    lg->sel = sel;
-    const size_t rows = (size_t)capacity * d.batch;
-    const size_t cnt8[] = {rows * d.nx, rows * d.nu, rows, rows, sep ? rows : 0};
-    const size_t cnt4[] = {rows, rows, sep ? rows : 0};
-    size_t bytes = 0;
-    for (size_t c : cnt8) bytes += (8 * c + 255) & ~size_t(255);
-    for (size_t c : cnt4) bytes += (4 * c + 255) & ~size_t(255);
-    if (hipMalloc(&lg->mem, bytes) != hipSuccess) {
-        lg->mem = nullptr;
+    lg->first = lg->end = h->rounds_done;
+    lg->d = cmpc_log_dims{d.batch, nx, nu, 3, d.N, look_col};
+    lg->sel = cmpc_nbr_dims{d.batch, d.N, 1, d.self_offset, d.n_total, 0, 0};
+    const size_t rows = (size_t)capacity * d.batch, sep_rows = sep ? rows : 0;
+    const size_t bytes = device_block(&lg->mem, {{lg->state, rows * nx}, {lg->u, rows * nu}, {lg->look, rows},
+                                                 {lg->kkt, rows}, {lg->sep2, sep_rows}, {lg->iters, rows},
+                                                 {lg->status, rows}, {lg->nearest, sep_rows}});
+    if (!bytes) {
         log_free(lg);
         return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the log ring failed");
-    }
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* p = lg->mem + off;
-        off += (b + 255) & ~size_t(255);
-        return p;
-    };
-    double** dp[] = {&lg->state, &lg->u, &lg->look, &lg->kkt, &lg->sep2};
-    for (int i = 0; i < 5; ++i) *dp[i] = reinterpret_cast<double*>(take(8 * cnt8[i]));
-    int** ip[] = {&lg->iters, &lg->status, &lg->nearest};
-    for (int i = 0; i < 3; ++i) *ip[i] = reinterpret_cast<int*>(take(4 * cnt4[i]));
-    if (!sep) {
-        lg->sep2 = nullptr;
-        lg->nearest = nullptr;
     }
     hipError_t e = hipMemsetAsync(lg->mem, 0, bytes, ctx->stream);
     for (int i = 0; e == hipSuccess && i < 2 * capacity; ++i) {
@@ -134,7 +261,7 @@ int log_enable(cmpc_ctx* ctx, RoundLog** out, int capacity, int flags, const cmp
         log_free(lg);
         return hip_fail(ctx, e, "log_enable");
     }
-    *out = lg;
+    h->log = lg;
     return CMPC_OK;
 }
 
@@ -149,30 +276,37 @@ void log_abandon(RoundLog* lg, int r) {
     if (lg) lg->first = std::max(lg->first, std::min(lg->end, r - lg->capacity + 1));
 }
 
-// round r's rows, stream-ordered after its exchange
-int log_round(cmpc_ctx* ctx, RoundLog* lg, int r, const double* z, const double* kkt, const int* iters,
-              const int* status, const double* traj_all, hipStream_t s) {
+// round r's rows, stream-ordered after its exchange; nothing with the log off
+int log_round(RoundsCore* h, int r, const double* z, const double* kkt, const int* iters, const int* status,
+              hipStream_t s) {
+    RoundLog* lg = h->log;
+    if (!lg) return CMPC_OK;
     const size_t row = (size_t)(r % lg->capacity) * lg->d.batch;
     const cmpc_log_row dst{lg->state + row * lg->d.nx, lg->u + row * lg->d.nu, lg->look + row,
                            lg->kkt + row, lg->iters + row, lg->status + row};
-    int rc = cmpc_round_log_dev(ctx, &lg->d, z, kkt, iters, status, &dst, s);
+    int rc = cmpc_round_log_dev(h->ctx, &lg->d, z, kkt, iters, status, &dst, s);
     if (rc == CMPC_OK && (lg->flags & CMPC_LOG_SEPARATION))
-        rc = cmpc_nbr_select_dev(ctx, &lg->sel, traj_all, lg->nearest + row, lg->sep2 + row, s);
+        rc = cmpc_nbr_select_dev(h->ctx, &lg->sel, h->traj_all, lg->nearest + row, lg->sep2 + row, s);
     if (rc != CMPC_OK) return rc;
     if (r != lg->end) lg->first = r;  // a round in between went unlogged (its exchange failed): the log restarts here
     lg->end = r + 1;
     return CMPC_OK;
 }
 
-int log_range(cmpc_ctx* ctx, const RoundLog* lg, int* first_round, int* count) {
-    if (!lg) return fail(ctx, CMPC_ERR_ARG, "the log is not enabled (log_enable)");
+int log_range(RoundsCore* h, int* first_round, int* count) {
+    if (!h) return CMPC_ERR_ARG;
+    const RoundLog* lg = h->log;
+    if (!lg) return fail(h->ctx, CMPC_ERR_ARG, "the log is not enabled (log_enable)");
     const int lo = std::max(lg->first, lg->end - lg->capacity);
     if (first_round) *first_round = lo;
     if (count) *count = lg->end - lo;
     return CMPC_OK;
 }
 
-int log_read(cmpc_ctx* ctx, const RoundLog* lg, int first_round, int count, const cmpc_rounds_log* o) {
+int log_read(RoundsCore* h, int first_round, int count, const cmpc_rounds_log* o) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    const RoundLog* lg = h->log;
     if (!lg) return fail(ctx, CMPC_ERR_ARG, "the log is not enabled (log_enable)");
     if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
     if (!(lg->flags & CMPC_LOG_SEPARATION) && (o->sep2 || o->nearest))
@@ -215,6 +349,8 @@ int log_read(cmpc_ctx* ctx, const RoundLog* lg, int first_round, int count, cons
 
 extern "C" {
 
+// ---- the reference's LPV agents (cmpc_lpv_rounds_*) ----
+
 int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc_track* track,
                            const cmpc_lpv_rounds_dims* dims, const cmpc_lpv_rounds_init* in, const cmpc_opts* opts,
                            cmpc_lpv_rounds** out) {
@@ -222,35 +358,18 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
     if (!out || !prm || !track || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
     *out = nullptr;
     const cmpc_lpv_rounds_dims& d = *dims;
-    if (d.N < 1 || d.nb < 0 || 4 + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
-        d.self_offset + d.batch > d.n_total)
-        return fail(ctx, CMPC_ERR_ARG, "bad rounds dimensions (1 <= batch, self_offset + batch <= n_total, nb <= 12)");
-    if (d.flags & ~(CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT))
-        return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
-    if ((d.flags & CMPC_ROUNDS_RESELECT) && d.nb >= d.n_total)
-        return fail(ctx, CMPC_ERR_ARG, "CMPC_ROUNDS_RESELECT selects nb < n_total neighbours");
+    const int rc = check_create(ctx, d, CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT, in->nbr,
+                                opts);
+    if (rc != CMPC_OK) return rc;
     if (track->nseg < 1 || track->nseg > CMPC_MAX_SEG) return fail(ctx, CMPC_ERR_UNSUPPORTED, "track has 1..32 segments");
-    if (!in->x0 || !in->x_last || !in->u_last || (d.nb > 0 && !in->nbr))
-        return fail(ctx, CMPC_ERR_ARG, "null initial state");
+    if (!in->x0 || !in->x_last || !in->u_last) return fail(ctx, CMPC_ERR_ARG, "null initial state");
     if (!in->traj && d.batch != d.n_total)
         return fail(ctx, CMPC_ERR_ARG, "a sharded population needs the initial exchange buffer (init->traj)");
-    if (d.batch != d.n_total && !(d.flags & CMPC_ROUNDS_HOST_EXCHANGE) &&
-        (!ctx->comm || (long)ctx->nranks * d.batch != d.n_total || ctx->rank * d.batch != d.self_offset))
-        return fail(ctx, CMPC_ERR_ARG,
-                    "a sharded population exchanges over the context's communicator (cmpc_comm_init: equal "
-                    "contiguous shards in rank order) or the host's (CMPC_ROUNDS_HOST_EXCHANGE)");
-    for (int i = 0; in->nbr && i < d.batch * d.nb; ++i)
-        if (in->nbr[i] < 0 || in->nbr[i] >= d.n_total) return fail(ctx, CMPC_ERR_ARG, "neighbour index out of range");
-    if (opts && (opts->flags & ~CMPC_FLAG_ALL)) return fail(ctx, CMPC_ERR_ARG, "unknown option flag");
     HIP_TRY(hipSetDevice(ctx->device));
 
     auto* h = new cmpc_lpv_rounds();
-    h->ctx = ctx;
+    core_init(h, ctx, d, opts);
     h->prm = *prm;
-    h->d = d;
-    if (opts) h->opts = *opts;
-    h->opts.stamps = nullptr;
-    h->opts.order = nullptr;
     h->last_rows = d.N + 1;
     const int ns = track->nseg;
     std::memcpy(h->seg[0], track->s0, sizeof(double) * ns);
@@ -259,48 +378,26 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
     std::memcpy(h->seg[3], track->half_width, sizeof(double) * ns);
     h->track = cmpc_track{ns, h->seg[0], h->seg[1], h->seg[2], h->seg[3]};
 
-    const size_t B = d.batch, N = d.N, nb = d.nb, T = d.n_total, row = (N + 1) * 2;
-    const size_t cnt[] = {B * 9, B * (N + 1) * 9, B * N * 2, B * 2, T * row, B * row, B * row,
-                          B * row * (nb ? nb : 1), B * nz_lpv(d.N), B * N * 3 * (nb ? nb : 1), B, B * N * 9};
-    size_t bytes = 0;
-    for (size_t c : cnt) bytes += ((8 * c + 255) & ~size_t(255));
-    bytes += 4 * ((B * (nb ? nb : 1) + 63) & ~size_t(63)) + 3 * 4 * ((B + 63) & ~size_t(63)) + 256;
-    if (hipMalloc(&h->mem, bytes) != hipSuccess) {
+    const size_t B = d.batch, N = d.N, nb1 = d.nb ? d.nb : 1, T = d.n_total, row = h->traj_row();
+    if (!device_block(&h->mem, {{h->x0, B * 9}, {h->x_last, B * (N + 1) * 9}, {h->u_last, B * N * 2}, {h->u_old, B * 2},
+                                {h->traj_all, T * row}, {h->traj_local, B * row}, {h->pose, B * row},
+                                {h->x_agents, B * row * nb1}, {h->z, B * nz_lpv(d.N)}, {h->planes, B * N * 3 * nb1},
+                                {h->kkt, B}, {h->x_dense, B * N * 9}, {h->nbr, B * nb1}, {h->iters, B}, {h->status, B},
+                                {h->infeasible, B}})) {
         delete h;
         return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
     }
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* p = h->mem + off;
-        off += (b + 255) & ~size_t(255);
-        return p;
-    };
-    double** dp[] = {&h->x0, &h->x_last, &h->u_last, &h->u_old, &h->traj_all, &h->traj_local, &h->pose,
-                     &h->x_agents, &h->z, &h->planes, &h->kkt, &h->x_dense};
-    for (int i = 0; i < 12; ++i) *dp[i] = reinterpret_cast<double*>(take(8 * cnt[i]));
-    h->nbr = reinterpret_cast<int*>(take(4 * B * (nb ? nb : 1)));
-    h->iters = reinterpret_cast<int*>(take(4 * B));
-    h->status = reinterpret_cast<int*>(take(4 * B));
-    h->infeasible = reinterpret_cast<int*>(take(4 * B));
-
     hipStream_t s = ctx->stream;
-    auto up = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s); };
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = up(h->x0, in->x0, 8 * B * 9);
-    if (e == hipSuccess) e = up(h->x_last, in->x_last, 8 * B * (N + 1) * 9);
-    if (e == hipSuccess) e = up(h->u_last, in->u_last, 8 * B * N * 2);
-    if (e == hipSuccess) e = in->u_old ? up(h->u_old, in->u_old, 8 * B * 2) : hipMemsetAsync(h->u_old, 0, 8 * B * 2, s);
-    if (e == hipSuccess && nb) e = up(h->nbr, in->nbr, 4 * B * nb);
-    if (e == hipSuccess) e = hipMemsetAsync(h->planes, 0, 8 * B * N * 3 * (nb ? nb : 1), s);
-    if (e == hipSuccess && in->traj) e = up(h->traj_all, in->traj, 8 * T * row);
+    hipError_t e = upload(h->x0, in->x0, 8 * B * 9, s);
+    if (e == hipSuccess) e = upload(h->x_last, in->x_last, 8 * B * (N + 1) * 9, s);
+    if (e == hipSuccess) e = upload(h->u_last, in->u_last, 8 * B * N * 2, s);
+    if (e == hipSuccess) e = in->u_old ? upload(h->u_old, in->u_old, 8 * B * 2, s) : hipMemsetAsync(h->u_old, 0, 8 * B * 2, s);
+    if (e == hipSuccess && d.nb) e = upload(h->nbr, in->nbr, 4 * B * d.nb, s);
+    if (e == hipSuccess) e = hipMemsetAsync(h->planes, 0, 8 * B * N * 3 * nb1, s);
+    if (e == hipSuccess && in->traj) e = upload(h->traj_all, in->traj, 8 * T * row, s);
     if (e == hipSuccess && !in->traj)  // the reference's initial `agents` = the predictions' X, Y (misc.py:155-165)
         e = hipMemcpy2DAsync(h->traj_all, 16, h->x_last + 7, 72, 16, B * (N + 1), hipMemcpyDeviceToDevice, s);
-    // this rank's rows of the exchange buffer: an agent that is not advanced keeps its initial ones
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(h->traj_local, h->traj_all + (size_t)d.self_offset * row, 8 * B * row,
-                           hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
+    if ((e = finish_uploads(h, e)) != hipSuccess) {
         (void)hipFree(h->mem);
         delete h;
         return hip_fail(ctx, e, "cmpc_lpv_rounds_create: upload");
@@ -312,22 +409,15 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
 int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* infeasible) {
     if (!h) return CMPC_ERR_ARG;
     cmpc_ctx* ctx = h->ctx;
-    if (rounds < 0) return fail(ctx, CMPC_ERR_ARG, "negative round count");
-    const bool host_x = h->d.flags & CMPC_ROUNDS_HOST_EXCHANGE, sharded = h->d.batch != h->d.n_total;
-    if (host_x && sharded && rounds > 1)
-        return fail(ctx, CMPC_ERR_ARG, "host exchange: one round per step (exchange between steps)");
+    int done = 0, bad = 0, rc;
+    if ((rc = check_step(h, rounds)) != CMPC_OK) return rc;
     const bool halt = !(h->d.flags & CMPC_ROUNDS_NO_HALT);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const cmpc_di_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset};
     const int nb = h->d.nb;
-    const cmpc_nbr_dims sd{h->d.batch, h->d.N, nb, h->d.self_offset, h->d.n_total, 0, 0};
-    int done = 0, bad = 0, rc;
+    const cmpc_di_dims rd{h->d.batch, h->d.N, nb, h->d.self_offset};
     for (int r = 0; r < rounds; ++r) {
-        // CMPC_ROUNDS_RESELECT: this round's neighbours are the nb nearest in the exchange buffer as it stands
-        if ((h->d.flags & CMPC_ROUNDS_RESELECT) &&
-            (rc = cmpc_nbr_select_dev(ctx, &sd, h->traj_all, h->nbr, nullptr, s)) != CMPC_OK)
-            return rc;
+        if ((rc = reselect(h, s)) != CMPC_OK) return rc;
         if ((rc = cmpc_lpv_gather_dev(ctx, &rd, h->nbr, h->traj_all, nb ? h->x_agents : nullptr, h->pose, s)) != CMPC_OK)
             return rc;
         const cmpc_lpv_dims ld{h->d.batch, h->d.N, nb, h->last_rows};
@@ -353,22 +443,15 @@ int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* 
                                        h->infeasible, s)) != CMPC_OK)
             return rc;
         h->last_rows = h->d.N;  // x_old = xPred[1:] from now on (LPV_HP_N_main.py:115)
-        const size_t row = 2 * (size_t)(h->d.N + 1);
-        if (!sharded) {
-            HIP_TRY(hipMemcpyAsync(h->traj_all, h->traj_local, 8 * row * h->d.batch, hipMemcpyDeviceToDevice, s));
-        } else if (!host_x) {
-            if ((rc = cmpc_allgather_trajectories(ctx, h->traj_local, h->traj_all, row * h->d.batch, s)) != CMPC_OK)
-                return rc;
-        }
+        if ((rc = exchange(h, s)) != CMPC_OK) return rc;
         // the node's infeasible count, not this rank's: the reference's loop quits for every agent
         // at once (LPV_HP_N_main.py:102-111), so every rank must take the same halt decision (a
         // rank that broke alone would leave the others waiting in the next round's all-gather).
         // The host exchange runs one round per step: its caller combines the counts it returns.
-        if (sharded && !host_x && (rc = cmpc_comm_sum_i32(ctx, h->infeasible, 1, s)) != CMPC_OK) return rc;
-        // the log's rows of this round (a round that halts the loop below has run, and is logged)
-        if (h->log && (rc = log_round(ctx, h->log, h->rounds_done, h->z, h->kkt, h->iters, h->status, h->traj_all,
-                                      s)) != CMPC_OK)
+        if (h->sharded() && !h->host_exchange() && (rc = cmpc_comm_sum_i32(ctx, h->infeasible, 1, s)) != CMPC_OK)
             return rc;
+        // the log's rows of this round (a round that halts the loop below has run, and is logged)
+        if ((rc = log_round(h, h->rounds_done, h->z, h->kkt, h->iters, h->status, s)) != CMPC_OK) return rc;
         ++h->rounds_done;
         ++done;
         if (halt || r + 1 == rounds) {  // the reference stops the experiment at an infeasible agent
@@ -401,57 +484,20 @@ int cmpc_lpv_rounds_read(cmpc_lpv_rounds* h, const cmpc_lpv_rounds_out* o) {
     return CMPC_OK;
 }
 
-int cmpc_lpv_rounds_get_traj(cmpc_lpv_rounds* h, double* traj_local) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (!traj_local) return fail(ctx, CMPC_ERR_ARG, "null buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(traj_local, h->traj_local, 16 * (size_t)(h->d.N + 1) * h->d.batch, hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CMPC_OK;
-}
-
-int cmpc_lpv_rounds_set_traj(cmpc_lpv_rounds* h, const double* traj_all) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (!traj_all) return fail(ctx, CMPC_ERR_ARG, "null buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(h->traj_all, traj_all, 16 * (size_t)(h->d.N + 1) * h->d.n_total, hipMemcpyHostToDevice,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CMPC_OK;
-}
-
-int cmpc_lpv_rounds_destroy(cmpc_lpv_rounds* h) {
-    if (!h) return CMPC_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    log_free(h->log);
-    (void)hipFree(h->mem);
-    delete h;
-    return CMPC_OK;
-}
-
+int cmpc_lpv_rounds_get_traj(cmpc_lpv_rounds* h, double* traj_local) { return get_traj(h, traj_local); }
+int cmpc_lpv_rounds_set_traj(cmpc_lpv_rounds* h, const double* traj_all) { return set_traj(h, traj_all); }
+int cmpc_lpv_rounds_destroy(cmpc_lpv_rounds* h) { return destroy(h); }
 int cmpc_lpv_rounds_log_enable(cmpc_lpv_rounds* h, int capacity, int flags) {
-    if (!h) return CMPC_ERR_ARG;
-    const cmpc_lpv_rounds_dims& d = h->d;
-    const cmpc_log_dims ld{d.batch, 9, 2, 3, d.N, 6};
-    const cmpc_nbr_dims sd{d.batch, d.N, 1, d.self_offset, d.n_total, 0, 0};
-    return log_enable(h->ctx, &h->log, capacity, flags, ld, sd,
-                      (d.flags & CMPC_ROUNDS_HOST_EXCHANGE) && d.batch != d.n_total, h->rounds_done);
+    return log_enable(h, capacity, flags, 9, 2, 6);
 }
-
 int cmpc_lpv_rounds_log_range(cmpc_lpv_rounds* h, int* first_round, int* count) {
-    return h ? log_range(h->ctx, h->log, first_round, count) : CMPC_ERR_ARG;
+    return log_range(h, first_round, count);
 }
-
 int cmpc_lpv_rounds_log_read(cmpc_lpv_rounds* h, int first_round, int count, const cmpc_rounds_log* o) {
-    return h ? log_read(h->ctx, h->log, first_round, count, o) : CMPC_ERR_ARG;
+    return log_read(h, first_round, count, o);
 }
 
 // ---- the synthetic double-integrator family (cmpc_di_rounds_*): what cmpc.rounds.DIRounds.step() chains ----
-//   [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 
 int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_mpc_weights* w,
                           const cmpc_di_rounds_dims* dims, const cmpc_di_rounds_init* in, const cmpc_opts* opts,
@@ -459,38 +505,22 @@ int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_m
     if (!ctx) return CMPC_ERR_ARG;
     if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
     *out = nullptr;
-    const cmpc_di_rounds_dims& d = *dims;
-    if (d.N < 1 || d.nb < 0 || 4 + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
-        d.self_offset + d.batch > d.n_total)
-        return fail(ctx, CMPC_ERR_ARG, "bad rounds dimensions (1 <= batch, self_offset + batch <= n_total, nb <= 12)");
+    const cmpc_lpv_rounds_dims d{dims->n_total, dims->batch, dims->self_offset, dims->N, dims->nb, dims->flags};
+    const int rc = check_create(
+        ctx, d, CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT, in->nbr, opts);
+    if (rc != CMPC_OK) return rc;
     if (prm->dim != 2 && prm->dim != 3) return fail(ctx, CMPC_ERR_ARG, "double-integrator agents have dim 2 or 3");
-    if (d.history < 0) return fail(ctx, CMPC_ERR_ARG, "negative history");
-    if (d.flags & ~(CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT))
-        return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
-    if ((d.flags & CMPC_ROUNDS_RESELECT) && d.nb >= d.n_total)
-        return fail(ctx, CMPC_ERR_ARG, "CMPC_ROUNDS_RESELECT selects nb < n_total neighbours");
+    if (dims->history < 0) return fail(ctx, CMPC_ERR_ARG, "negative history");
     if (!w->Q || !w->R || !w->dR || !w->Qs || !w->u_ub || !w->u_lb || !w->row_slack || !w->row_sign)
         return fail(ctx, CMPC_ERR_ARG, "null weights");
-    if (!in->A || !in->B || !in->x0 || !in->u_prev || !in->lane || !in->traj || (d.nb > 0 && !in->nbr))
+    if (!in->A || !in->B || !in->x0 || !in->u_prev || !in->lane || !in->traj)
         return fail(ctx, CMPC_ERR_ARG, "null initial state");
-    if (d.batch != d.n_total && !(d.flags & CMPC_ROUNDS_HOST_EXCHANGE) &&
-        (!ctx->comm || (long)ctx->nranks * d.batch != d.n_total || ctx->rank * d.batch != d.self_offset))
-        return fail(ctx, CMPC_ERR_ARG,
-                    "a sharded population exchanges over the context's communicator (cmpc_comm_init: equal "
-                    "contiguous shards in rank order) or the host's (CMPC_ROUNDS_HOST_EXCHANGE)");
-    for (int i = 0; in->nbr && i < d.batch * d.nb; ++i)
-        if (in->nbr[i] < 0 || in->nbr[i] >= d.n_total) return fail(ctx, CMPC_ERR_ARG, "neighbour index out of range");
-    if (opts && (opts->flags & ~CMPC_FLAG_ALL)) return fail(ctx, CMPC_ERR_ARG, "unknown option flag");
     HIP_TRY(hipSetDevice(ctx->device));
 
     auto* h = new cmpc_di_rounds();
-    h->ctx = ctx;
+    core_init(h, ctx, d, opts);
     h->prm = *prm;
-    h->d = d;
-    if (h->d.history == 0) h->d.history = 1;
-    if (opts) h->opts = *opts;
-    h->opts.stamps = nullptr;
-    h->opts.order = nullptr;
+    h->history = std::max(dims->history, 1);
     const int nx = 2 * prm->dim, nu = prm->dim, mc = 4 + d.nb;
     h->md = cmpc_mpc_dims{nx, nu, d.N, 3, mc, d.batch};
     std::memcpy(h->Q, w->Q, sizeof(double) * nx * nx);
@@ -503,47 +533,27 @@ int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_m
     std::memcpy(h->row_sign, w->row_sign, sizeof(int) * mc);
     h->w = cmpc_mpc_weights{h->Q, h->R, h->dR, h->Qs, h->u_ub, h->u_lb, h->row_slack, h->row_sign};
 
-    const size_t B = d.batch, N = d.N, nb = d.nb, T = d.n_total, row = (N + 1) * 2, H = h->d.history;
-    const size_t cnt[] = {B * N * nx * nx, B * N * nx * nu, B * nx, B * nu, B, T * row, B * row,
-                          B * (N + 1) * nx, B * N * mc * nx, B * N * mc, B * nz_di(nx, nu, d.N), H * B};
-    size_t bytes = 0;
-    for (size_t c : cnt) bytes += ((8 * c + 255) & ~size_t(255));
-    bytes += ((4 * B * (nb ? nb : 1) + 255) & ~size_t(255)) + 2 * ((4 * H * B + 255) & ~size_t(255)) +
-             ((4 * B + 255) & ~size_t(255));
-    if (hipMalloc(&h->mem, bytes) != hipSuccess) {
+    const size_t B = d.batch, N = d.N, nb1 = d.nb ? d.nb : 1, T = d.n_total, row = h->traj_row(), H = h->history;
+    const size_t nA = B * N * nx * nx, nB = B * N * nx * nu;
+    const size_t bytes = device_block(
+        &h->mem, {{h->A, nA}, {h->B, nB}, {h->x0, B * nx}, {h->u_prev, B * nu}, {h->lane, B}, {h->traj_all, T * row},
+                  {h->traj_local, B * row}, {h->qlin, B * (N + 1) * nx}, {h->C, B * N * mc * nx}, {h->h, B * N * mc},
+                  {h->z, B * nz_di(nx, nu, d.N)}, {h->kkt, H * B}, {h->nbr, B * nb1}, {h->iters, H * B},
+                  {h->status, H * B}, {h->order, B}});
+    if (!bytes) {
         delete h;
         return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
     }
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* p = h->mem + off;
-        off += (b + 255) & ~size_t(255);
-        return p;
-    };
-    double** dp[] = {&h->A, &h->B, &h->x0, &h->u_prev, &h->lane, &h->traj_all, &h->traj_local, &h->qlin, &h->C,
-                     &h->h, &h->z, &h->kkt};
-    for (int i = 0; i < 12; ++i) *dp[i] = reinterpret_cast<double*>(take(8 * cnt[i]));
-    h->nbr = reinterpret_cast<int*>(take(4 * B * (nb ? nb : 1)));
-    h->iters = reinterpret_cast<int*>(take(4 * H * B));
-    h->status = reinterpret_cast<int*>(take(4 * H * B));
-    h->order = reinterpret_cast<int*>(take(4 * B));
-
     hipStream_t s = ctx->stream;
-    auto up = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s); };
     hipError_t e = hipMemsetAsync(h->mem, 0, bytes, s);  // a read before the first round returns zeros
-    if (e == hipSuccess) e = up(h->A, in->A, 8 * cnt[0]);
-    if (e == hipSuccess) e = up(h->B, in->B, 8 * cnt[1]);
-    if (e == hipSuccess) e = up(h->x0, in->x0, 8 * cnt[2]);
-    if (e == hipSuccess) e = up(h->u_prev, in->u_prev, 8 * cnt[3]);
-    if (e == hipSuccess) e = up(h->lane, in->lane, 8 * cnt[4]);
-    if (e == hipSuccess) e = up(h->traj_all, in->traj, 8 * cnt[5]);
-    if (e == hipSuccess && nb) e = up(h->nbr, in->nbr, 4 * B * nb);
-    // this rank's rows of the exchange buffer until the first round writes them
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(h->traj_local, h->traj_all + (size_t)d.self_offset * row, 8 * B * row,
-                           hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
+    if (e == hipSuccess) e = upload(h->A, in->A, 8 * nA, s);
+    if (e == hipSuccess) e = upload(h->B, in->B, 8 * nB, s);
+    if (e == hipSuccess) e = upload(h->x0, in->x0, 8 * B * nx, s);
+    if (e == hipSuccess) e = upload(h->u_prev, in->u_prev, 8 * B * nu, s);
+    if (e == hipSuccess) e = upload(h->lane, in->lane, 8 * B, s);
+    if (e == hipSuccess) e = upload(h->traj_all, in->traj, 8 * T * row, s);
+    if (e == hipSuccess && d.nb) e = upload(h->nbr, in->nbr, 4 * B * d.nb, s);
+    if ((e = finish_uploads(h, e)) != hipSuccess) {
         (void)hipFree(h->mem);
         delete h;
         return hip_fail(ctx, e, "cmpc_di_rounds_create: upload");
@@ -556,36 +566,29 @@ int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done) {
     if (!h) return CMPC_ERR_ARG;
     cmpc_ctx* ctx = h->ctx;
     if (rounds_done) *rounds_done = 0;
-    if (rounds < 0) return fail(ctx, CMPC_ERR_ARG, "negative round count");
-    const bool host_x = h->d.flags & CMPC_ROUNDS_HOST_EXCHANGE, sharded = h->d.batch != h->d.n_total;
-    if (host_x && sharded && rounds > 1)
-        return fail(ctx, CMPC_ERR_ARG, "host exchange: one round per step (exchange between steps)");
+    int done = 0, rc;
+    if ((rc = check_step(h, rounds)) != CMPC_OK) return rc;
     const bool lpt = h->d.flags & CMPC_ROUNDS_LPT;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t B = h->d.batch, row = 2 * (size_t)(h->d.N + 1);
     const cmpc_di_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset};
-    const cmpc_nbr_dims sd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->d.n_total, 0, 0};
     const cmpc_mpc_data din{h->A, h->B, h->x0, h->u_prev, h->qlin, h->C, h->h};
-    int done = 0, rc = CMPC_OK;
     for (int r = 0; r < rounds && rc == CMPC_OK; ++r) {
-        const size_t slot = (size_t)(h->rounds_done % h->d.history) * B;  // this round's row of the history ring
+        const int round = h->rounds_done;
+        const size_t slot = (size_t)(round % h->history) * h->d.batch;  // this round's row of the history ring
         const cmpc_mpc_out dout{h->z, h->kkt + slot, h->iters + slot, h->status + slot};
-        if ((h->d.flags & CMPC_ROUNDS_RESELECT) && h->d.nb > 0 &&
-            (rc = cmpc_nbr_select_dev(ctx, &sd, h->traj_all, h->nbr, nullptr, s)) != CMPC_OK)
-            break;
-        h->opts.order = (lpt && h->rounds_done > 0) ? h->order : nullptr;
-        hipError_t ev = log_mark(h->log, h->rounds_done, 0, s);
+        if ((rc = reselect(h, s)) != CMPC_OK) break;
+        h->opts.order = (lpt && round > 0) ? h->order : nullptr;
+        hipError_t ev = log_mark(h->log, round, 0, s);
+        if (ev == hipSuccess) {
+            if ((rc = cmpc_di_round_dev(ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w, &din, &dout,
+                                        &h->opts, h->traj_local, s)) != CMPC_OK) {
+                log_abandon(h->log, round);
+                break;
+            }
+            ev = log_mark(h->log, round, 1, s);
+        }
         if (ev != hipSuccess) {
-            rc = hip_fail(ctx, ev, "cmpc_di_rounds_step: log event");
-            break;
-        }
-        if ((rc = cmpc_di_round_dev(ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w, &din, &dout,
-                                    &h->opts, h->traj_local, s)) != CMPC_OK) {
-            log_abandon(h->log, h->rounds_done);
-            break;
-        }
-        if ((ev = log_mark(h->log, h->rounds_done, 1, s)) != hipSuccess) {
             rc = hip_fail(ctx, ev, "cmpc_di_rounds_step: log event");
             break;
         }
@@ -593,16 +596,9 @@ int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done) {
         if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) break;
         ++h->rounds_done;  // the round's outputs exist from here on, whatever the exchange returns
         ++done;
-        if (!sharded) {
-            hipError_t e = hipMemcpyAsync(h->traj_all, h->traj_local, 8 * row * B, hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) rc = hip_fail(ctx, e, "cmpc_di_rounds_step: exchange");
-        } else if (!host_x) {
-            rc = cmpc_allgather_trajectories(ctx, h->traj_local, h->traj_all, row * B, s);
-        }
         // the log's rows of this round, from the history-ring row the solver wrote
-        if (h->log && rc == CMPC_OK)
-            rc = log_round(ctx, h->log, h->rounds_done - 1, h->z, h->kkt + slot, h->iters + slot, h->status + slot,
-                           h->traj_all, s);
+        if ((rc = exchange(h, s)) == CMPC_OK)
+            rc = log_round(h, round, h->z, h->kkt + slot, h->iters + slot, h->status + slot, s);
     }
     // one host synchronisation, also after an error: the rounds already queued have then finished
     const hipError_t e = hipStreamSynchronize(s);
@@ -619,7 +615,7 @@ int cmpc_di_rounds_read(cmpc_di_rounds* h, const cmpc_di_rounds_out* o) {
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t B = h->d.batch;
-    const size_t slot = (size_t)((h->rounds_done > 0 ? h->rounds_done - 1 : 0) % h->d.history) * B;
+    const size_t slot = (size_t)((h->rounds_done > 0 ? h->rounds_done - 1 : 0) % h->history) * B;
     auto dn = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s); };
     if (o->z) HIP_TRY(dn(o->z, h->z, 8 * B * nz_di(h->md.nx, h->md.nu, h->d.N)));
     if (o->kkt) HIP_TRY(dn(o->kkt, h->kkt + slot, 8 * B));
@@ -637,13 +633,13 @@ int cmpc_di_rounds_history(cmpc_di_rounds* h, int first_round, int count, double
     cmpc_ctx* ctx = h->ctx;
     if (first_round < 0 || count < 0 || (long long)first_round + count > h->rounds_done)
         return fail(ctx, CMPC_ERR_ARG, "history: a round that has not run yet");
-    if (count > 0 && first_round < h->rounds_done - h->d.history)
+    if (count > 0 && first_round < h->rounds_done - h->history)
         return fail(ctx, CMPC_ERR_ARG, "history: a round the ring has already overwritten (dims.history rounds are kept)");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t B = h->d.batch;
     for (int i = 0; i < count; ++i) {
-        const size_t slot = (size_t)((first_round + i) % h->d.history) * B;
+        const size_t slot = (size_t)((first_round + i) % h->history) * B;
         if (kkt) HIP_TRY(hipMemcpyAsync(kkt + i * B, h->kkt + slot, 8 * B, hipMemcpyDeviceToHost, s));
         if (iters) HIP_TRY(hipMemcpyAsync(iters + i * B, h->iters + slot, 4 * B, hipMemcpyDeviceToHost, s));
         if (status) HIP_TRY(hipMemcpyAsync(status + i * B, h->status + slot, 4 * B, hipMemcpyDeviceToHost, s));
@@ -652,53 +648,15 @@ int cmpc_di_rounds_history(cmpc_di_rounds* h, int first_round, int count, double
     return CMPC_OK;
 }
 
-int cmpc_di_rounds_get_traj(cmpc_di_rounds* h, double* traj_local) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (!traj_local) return fail(ctx, CMPC_ERR_ARG, "null buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(traj_local, h->traj_local, 16 * (size_t)(h->d.N + 1) * h->d.batch, hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CMPC_OK;
-}
-
-int cmpc_di_rounds_set_traj(cmpc_di_rounds* h, const double* traj_all) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (!traj_all) return fail(ctx, CMPC_ERR_ARG, "null buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(h->traj_all, traj_all, 16 * (size_t)(h->d.N + 1) * h->d.n_total, hipMemcpyHostToDevice,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CMPC_OK;
-}
-
-int cmpc_di_rounds_destroy(cmpc_di_rounds* h) {
-    if (!h) return CMPC_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    log_free(h->log);
-    (void)hipFree(h->mem);
-    delete h;
-    return CMPC_OK;
-}
-
+int cmpc_di_rounds_get_traj(cmpc_di_rounds* h, double* traj_local) { return get_traj(h, traj_local); }
+int cmpc_di_rounds_set_traj(cmpc_di_rounds* h, const double* traj_all) { return set_traj(h, traj_all); }
+int cmpc_di_rounds_destroy(cmpc_di_rounds* h) { return destroy(h); }
 int cmpc_di_rounds_log_enable(cmpc_di_rounds* h, int capacity, int flags) {
-    if (!h) return CMPC_ERR_ARG;
-    const cmpc_di_rounds_dims& d = h->d;
-    const cmpc_log_dims ld{d.batch, h->md.nx, h->md.nu, 3, d.N, 0};
-    const cmpc_nbr_dims sd{d.batch, d.N, 1, d.self_offset, d.n_total, 0, 0};
-    return log_enable(h->ctx, &h->log, capacity, flags, ld, sd,
-                      (d.flags & CMPC_ROUNDS_HOST_EXCHANGE) && d.batch != d.n_total, h->rounds_done);
+    return h ? log_enable(h, capacity, flags, h->md.nx, h->md.nu, 0) : CMPC_ERR_ARG;
 }
-
-int cmpc_di_rounds_log_range(cmpc_di_rounds* h, int* first_round, int* count) {
-    return h ? log_range(h->ctx, h->log, first_round, count) : CMPC_ERR_ARG;
-}
-
+int cmpc_di_rounds_log_range(cmpc_di_rounds* h, int* first_round, int* count) { return log_range(h, first_round, count); }
 int cmpc_di_rounds_log_read(cmpc_di_rounds* h, int first_round, int count, const cmpc_rounds_log* o) {
-    return h ? log_read(h->ctx, h->log, first_round, count, o) : CMPC_ERR_ARG;
+    return log_read(h, first_round, count, o);
 }
 
 }  // extern "C"

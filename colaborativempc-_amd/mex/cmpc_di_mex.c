@@ -43,62 +43,9 @@
 #include "cmpc.h"
 #include "mex.h"
 
-#define MAX_HANDLES 64
-
-static cmpc_ctx* g_ctx = NULL;
-static cmpc_di_rounds* g_h[MAX_HANDLES];
-static int g_hN[MAX_HANDLES], g_hB[MAX_HANDLES], g_hnb[MAX_HANDLES], g_hT[MAX_HANDLES], g_hdim[MAX_HANDLES];
-static int g_hlog[MAX_HANDLES]; /* CMPC_LOG_* flags of rounds_log_enable */
-
-static void cleanup(void) {
-    for (int i = 0; i < MAX_HANDLES; ++i)
-        if (g_h[i]) {
-            cmpc_di_rounds_destroy(g_h[i]);
-            g_h[i] = NULL;
-        }
-    if (g_ctx) cmpc_destroy(g_ctx);
-    g_ctx = NULL;
-}
-
-static void ensure_ctx(void) {
-    if (!g_ctx) {
-        if (cmpc_create(&g_ctx, 0) != CMPC_OK) {
-            g_ctx = NULL;
-            mexErrMsgIdAndTxt("cmpc:device", "cmpc_di: no usable MI355X (gfx950) device");
-        }
-        mexAtExit(cleanup);
-    }
-}
-
-static void check(int rc, const char* what) {
-    if (rc != CMPC_OK) mexErrMsgIdAndTxt("cmpc:solve", "%s failed (%d): %s", what, rc, cmpc_last_error(g_ctx));
-}
-
-static const mxArray* field(const mxArray* S, const char* name, size_t numel, int required) {
-    const mxArray* v = mxGetField(S, 0, name);
-    if (!v || mxIsEmpty(v)) {
-        if (required) mexErrMsgIdAndTxt("cmpc:di:args", "field %s is required", name);
-        return NULL;
-    }
-    if (!mxIsDouble(v) || mxIsComplex(v) || mxIsSparse(v))
-        mexErrMsgIdAndTxt("cmpc:di:args", "field %s must be a full real double array", name);
-    if (numel && mxGetNumberOfElements(v) != numel)
-        mexErrMsgIdAndTxt("cmpc:di:args", "field %s has %zu elements, expected %zu", name, mxGetNumberOfElements(v),
-                          numel);
-    return v;
-}
-
-static double scalar(const mxArray* S, const char* name) { return mxGetScalar(field(S, name, 1, 1)); }
-
-static double scalar_or(const mxArray* S, const char* name, double dflt) {
-    const mxArray* v = field(S, name, 1, 0);
-    return v ? mxGetScalar(v) : dflt;
-}
-
-static const mxArray* require_struct(const mxArray* a, const char* what) {
-    if (!a || !mxIsStruct(a)) mexErrMsgIdAndTxt("cmpc:di:args", "%s must be a struct", what);
-    return a;
-}
+#define CMPC_MEX_FAMILY cmpc_di
+#define CMPC_MEX_ARGS "cmpc:di:args"
+#include "cmpc_mex_rounds.h"
 
 /* n x n, MATLAB column-major -> row-major */
 static void square(const mxArray* P, const char* name, int n, double* out) {
@@ -107,33 +54,25 @@ static void square(const mxArray* P, const char* name, int n, double* out) {
         for (int j = 0; j < n; ++j) out[i * n + j] = m[j * n + i];
 }
 
-static int handle_of(const mxArray* a) {
-    if (!a || !mxIsDouble(a) || mxGetNumberOfElements(a) != 1) mexErrMsgIdAndTxt("cmpc:di:args", "bad rounds handle");
-    const int h = (int)mxGetScalar(a) - 1;
-    if (h < 0 || h >= MAX_HANDLES || !g_h[h]) mexErrMsgIdAndTxt("cmpc:di:args", "bad rounds handle");
-    return h;
-}
-
-static void rounds_create(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    if (nrhs != 4) mexErrMsgIdAndTxt("cmpc:di:args", "usage: h = cmpc_di('rounds_create', P, D, S)");
+static void rounds_create(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs != 4) ARGS_ERROR("usage: h = cmpc_di('rounds_create', P, D, S)");
     const mxArray* P = require_struct(prhs[1], "P");
     const mxArray* D = require_struct(prhs[2], "D");
     const mxArray* S = require_struct(prhs[3], "S");
     cmpc_di_params prm;
     memset(&prm, 0, sizeof prm);
     prm.dim = (int)scalar(P, "dim");
-    if (prm.dim != 2 && prm.dim != 3) mexErrMsgIdAndTxt("cmpc:di:args", "P.dim must be 2 or 3");
+    if (prm.dim != 2 && prm.dim != 3) ARGS_ERROR("P.dim must be 2 or 3");
     prm.v_ref = scalar(P, "v_ref"); prm.q_v = scalar(P, "q_v"); prm.q_lane = scalar(P, "q_lane");
     prm.hw = scalar(P, "hw"); prm.min_vel = scalar(P, "min_vel"); prm.max_vel = scalar(P, "max_vel");
     prm.min_dist = scalar(P, "min_dist"); prm.wq = scalar(P, "wq");
     const int N = (int)scalar(P, "N");
-    if (N < 1) mexErrMsgIdAndTxt("cmpc:di:args", "P.N must be >= 1");
+    if (N < 1) ARGS_ERROR("P.N must be >= 1");
     const int nx = 2 * prm.dim, nu = prm.dim;
 
     const mxArray* x0 = field(D, "x0", 0, 1);
     const size_t B = mxGetNumberOfElements(x0) / (size_t)nx;
-    if (B * nx != mxGetNumberOfElements(x0) || B == 0) mexErrMsgIdAndTxt("cmpc:di:args", "x0 must be nx x B");
+    if (B * nx != mxGetNumberOfElements(x0) || B == 0) ARGS_ERROR("x0 must be nx x B");
     const mxArray* A = field(D, "A", (size_t)nx * nx * N * B, 1);
     const mxArray* Bm = field(D, "B", (size_t)nu * nx * N * B, 1);
     const mxArray* up = field(D, "u_prev", (size_t)nu * B, 1);
@@ -141,11 +80,11 @@ static void rounds_create(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
 
     const int n_total = (int)scalar_or(S, "n_total", (double)B);
     const int self_offset = (int)scalar_or(S, "self_offset", 0.0);
-    if (n_total < 1) mexErrMsgIdAndTxt("cmpc:di:args", "S.n_total must be >= 1");
+    if (n_total < 1) ARGS_ERROR("S.n_total must be >= 1");
     const mxArray* nbr = field(S, "nbr", 0, 0);
     const int nb = nbr ? (int)(mxGetNumberOfElements(nbr) / B) : 0;
-    if (nbr && (size_t)nb * B != mxGetNumberOfElements(nbr)) mexErrMsgIdAndTxt("cmpc:di:args", "nbr must be nb x B");
-    if (4 + nb > CMPC_MAX_MC) mexErrMsgIdAndTxt("cmpc:di:args", "at most %d neighbours per agent", CMPC_MAX_MC - 4);
+    if (nbr && (size_t)nb * B != mxGetNumberOfElements(nbr)) ARGS_ERROR("nbr must be nb x B");
+    if (4 + nb > CMPC_MAX_MC) ARGS_ERROR("at most %d neighbours per agent", CMPC_MAX_MC - 4);
     const mxArray* traj = field(S, "traj", 2 * (size_t)(N + 1) * n_total, 1);
     const int mc = 4 + nb;
 
@@ -172,47 +111,29 @@ static void rounds_create(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
                       (scalar_or(S, "reselect", 0.0) != 0.0 ? CMPC_ROUNDS_RESELECT : 0) |
                       (scalar_or(S, "lpt", 0.0) != 0.0 ? CMPC_ROUNDS_LPT : 0);
     const cmpc_di_rounds_dims dims = {n_total, (int)B, self_offset, N, nb, flags, (int)scalar_or(S, "history", 1.0)};
-    int slot = -1;
-    for (int i = 0; i < MAX_HANDLES && slot < 0; ++i)
-        if (!g_h[i]) slot = i;
-    if (slot < 0) mexErrMsgIdAndTxt("cmpc:di:args", "too many open rounds handles (%d)", MAX_HANDLES);
-    int* inbr = (int*)mxCalloc((size_t)(nb ? nb : 1) * B, sizeof(int));
-    for (size_t i = 0; nbr && i < (size_t)nb * B; ++i) inbr[i] = (int)mxGetPr(nbr)[i];
+    const int slot = free_slot();
+    int* inbr = nbr_ints(nbr, (size_t)nb * B);
     const cmpc_di_rounds_init init = {mxGetPr(A), mxGetPr(Bm), mxGetPr(x0), mxGetPr(up), mxGetPr(lane), inbr,
                                       mxGetPr(traj)};
     ensure_ctx();
-    const int rc = cmpc_di_rounds_create(g_ctx, &prm, &w, &dims, &init, &opts, &g_h[slot]);
+    const int rc = cmpc_di_rounds_create(g_ctx, &prm, &w, &dims, &init, &opts, &g_tab[slot].h);
     mxFree(inbr);
     check(rc, "cmpc_di_rounds_create");
-    g_hN[slot] = N;
-    g_hB[slot] = (int)B;
-    g_hnb[slot] = nb;
-    g_hT[slot] = n_total;
-    g_hdim[slot] = prm.dim;
-    g_hlog[slot] = 0;
-    plhs[0] = mxCreateDoubleMatrix(1, 1, mxREAL);
-    mxGetPr(plhs[0])[0] = slot + 1;
+    g_tab[slot] = (rounds_slot){g_tab[slot].h, N, (int)B, nb, n_total, nx, nu, 0};
+    plhs[0] = scalar_out(slot + 1);
 }
 
-static void rounds_step(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    if (nrhs != 3) mexErrMsgIdAndTxt("cmpc:di:args", "usage: done = cmpc_di('rounds_step', h, k)");
-    const int h = handle_of(prhs[1]);
+static void rounds_step(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs != 3) ARGS_ERROR("usage: done = cmpc_di('rounds_step', h, k)");
     int done = 0;
-    check(cmpc_di_rounds_step(g_h[h], (int)mxGetScalar(prhs[2]), &done), "cmpc_di_rounds_step");
-    plhs[0] = mxCreateDoubleMatrix(1, 1, mxREAL);
-    mxGetPr(plhs[0])[0] = done;
-}
-
-static void widen(mxArray* dst, const int* src, size_t n) {
-    for (size_t i = 0; i < n; ++i) mxGetPr(dst)[i] = src[i];
+    check(cmpc_di_rounds_step(handle_of(prhs[1])->h, (int)mxGetScalar(prhs[2]), &done), "cmpc_di_rounds_step");
+    plhs[0] = scalar_out(done);
 }
 
 static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    if (nrhs != 2)
-        mexErrMsgIdAndTxt("cmpc:di:args", "usage: [z, status, kkt, iters, x0, u_prev, nbr] = cmpc_di('rounds_read', h)");
-    const int h = handle_of(prhs[1]);
-    const int N = g_hN[h], B = g_hB[h], nb = g_hnb[h], nx = 2 * g_hdim[h], nu = g_hdim[h];
+    if (nrhs != 2) ARGS_ERROR("usage: [z, status, kkt, iters, x0, u_prev, nbr] = cmpc_di('rounds_read', h)");
+    const rounds_slot* t = handle_of(prhs[1]);
+    const int N = t->N, B = t->B, nb = t->nb, nx = t->nx, nu = t->nu;
     const size_t nz = (size_t)(nx + 3) * (N + 1) + 2 * (size_t)nu * N;
     mxArray* Z = mxCreateDoubleMatrix(nz, B, mxREAL);
     mxArray* ST = mxCreateDoubleMatrix(1, B, mxREAL);
@@ -225,7 +146,7 @@ static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     int* status = (int*)mxCalloc(B, sizeof(int));
     int* inbr = (int*)mxCalloc((size_t)(nb ? nb : 1) * B, sizeof(int));
     const cmpc_di_rounds_out o = {mxGetPr(Z), mxGetPr(KK), iters, status, mxGetPr(X0), mxGetPr(UP), nb ? inbr : NULL};
-    const int rc = cmpc_di_rounds_read(g_h[h], &o);
+    const int rc = cmpc_di_rounds_read(t->h, &o);
     if (rc == CMPC_OK) {
         widen(IT, iters, B);
         widen(ST, status, B);
@@ -245,18 +166,17 @@ static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
 }
 
 static void rounds_history(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    if (nrhs != 4)
-        mexErrMsgIdAndTxt("cmpc:di:args", "usage: [kkt, iters, status] = cmpc_di('rounds_history', h, first, count)");
-    const int h = handle_of(prhs[1]);
-    const int first = (int)mxGetScalar(prhs[2]), count = (int)mxGetScalar(prhs[3]), B = g_hB[h];
-    if (first < 0 || count < 0) mexErrMsgIdAndTxt("cmpc:di:args", "first and count must be >= 0");
+    if (nrhs != 4) ARGS_ERROR("usage: [kkt, iters, status] = cmpc_di('rounds_history', h, first, count)");
+    const rounds_slot* t = handle_of(prhs[1]);
+    const int first = (int)mxGetScalar(prhs[2]), count = (int)mxGetScalar(prhs[3]), B = t->B;
+    if (first < 0 || count < 0) ARGS_ERROR("first and count must be >= 0");
     const size_t n = (size_t)B * count;
     mxArray* KK = mxCreateDoubleMatrix(B, count, mxREAL);
     mxArray* IT = mxCreateDoubleMatrix(B, count, mxREAL);
     mxArray* ST = mxCreateDoubleMatrix(B, count, mxREAL);
     int* iters = (int*)mxCalloc(n ? n : 1, sizeof(int));
     int* status = (int*)mxCalloc(n ? n : 1, sizeof(int));
-    const int rc = cmpc_di_rounds_history(g_h[h], first, count, mxGetPr(KK), iters, status);
+    const int rc = cmpc_di_rounds_history(t->h, first, count, mxGetPr(KK), iters, status);
     if (rc == CMPC_OK) {
         widen(IT, iters, n);
         widen(ST, status, n);
@@ -269,118 +189,21 @@ static void rounds_history(int nlhs, mxArray* plhs[], int nrhs, const mxArray* p
     if (nlhs > 2) plhs[2] = ST;
 }
 
-static void rounds_log_enable(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    (void)plhs;
-    if (nrhs != 3 && nrhs != 4)
-        mexErrMsgIdAndTxt("cmpc:di:args", "usage: cmpc_di('rounds_log_enable', h, capacity [, flags])");
-    const int h = handle_of(prhs[1]);
-    const int flags = nrhs > 3 ? (int)mxGetScalar(prhs[3]) : 0;
-    check(cmpc_di_rounds_log_enable(g_h[h], (int)mxGetScalar(prhs[2]), flags), "cmpc_di_rounds_log_enable");
-    g_hlog[h] = flags;
-}
-
-static void rounds_log(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    if (nrhs != 2 && nrhs != 4) mexErrMsgIdAndTxt("cmpc:di:args", "usage: L = cmpc_di('rounds_log', h [, first, count])");
-    const int h = handle_of(prhs[1]);
-    const int B = g_hB[h], nx = 2 * g_hdim[h], nu = g_hdim[h], sep = g_hlog[h] & CMPC_LOG_SEPARATION;
-    int first = 0, count = 0;
-    if (nrhs == 2) {
-        check(cmpc_di_rounds_log_range(g_h[h], &first, &count), "cmpc_di_rounds_log_range");
-    } else {
-        first = (int)mxGetScalar(prhs[2]);
-        count = (int)mxGetScalar(prhs[3]);
-    }
-    if (first < 0 || count < 0) mexErrMsgIdAndTxt("cmpc:di:args", "first and count must be >= 0");
-    const size_t n = (size_t)B * count;
-    const mwSize ds[3] = {(mwSize)nx, (mwSize)B, (mwSize)count}, du[3] = {(mwSize)nu, (mwSize)B, (mwSize)count};
-    mxArray* XS = mxCreateNumericArray(3, ds, mxDOUBLE_CLASS, mxREAL);
-    mxArray* US = mxCreateNumericArray(3, du, mxDOUBLE_CLASS, mxREAL);
-    mxArray* LA = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* KK = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* IT = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* ST = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* S2 = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* NR = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* MS = mxCreateDoubleMatrix(count, 1, mxREAL);
-    int* ibuf = (int*)mxCalloc(3 * (n ? n : 1), sizeof(int));
-    int *iters = ibuf, *status = ibuf + (n ? n : 1), *nearest = status + (n ? n : 1);
-    const cmpc_rounds_log o = {mxGetPr(XS), mxGetPr(US), mxGetPr(LA), mxGetPr(KK), iters, status,
-                               sep ? mxGetPr(S2) : NULL, sep ? nearest : NULL, mxGetPr(MS)};
-    const int rc = cmpc_di_rounds_log_read(g_h[h], first, count, &o);
-    if (rc == CMPC_OK) {
-        widen(IT, iters, n);
-        widen(ST, status, n);
-        if (sep) widen(NR, nearest, n);
-    }
-    mxFree(ibuf);
-    check(rc, "cmpc_di_rounds_log_read");
-    const char* names[] = {"first", "state", "u", "look_ahead", "kkt", "iters", "status", "solve_ms", "sep2", "nearest"};
-    mxArray* L = mxCreateStructMatrix(1, 1, sep ? 10 : 8, names);
-    mxArray* F = mxCreateDoubleMatrix(1, 1, mxREAL);
-    mxGetPr(F)[0] = first;
-    mxArray* vals[] = {F, XS, US, LA, KK, IT, ST, MS, S2, NR};
-    for (int i = 0; i < (sep ? 10 : 8); ++i) mxSetField(L, 0, names[i], vals[i]);
-    plhs[0] = L;
-}
-
-static void rounds_traj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int set) {
-    (void)nlhs;
-    if (nrhs != (set ? 3 : 2)) mexErrMsgIdAndTxt("cmpc:di:args", "usage: rounds_get_traj(h) / rounds_set_traj(h, T)");
-    const int h = handle_of(prhs[1]);
-    const int N = g_hN[h];
-    if (set) {
-        const mxArray* T = prhs[2];
-        if (!mxIsDouble(T) || mxGetNumberOfElements(T) != 2 * (size_t)(N + 1) * g_hT[h])
-            mexErrMsgIdAndTxt("cmpc:di:args", "T must be 2 x (N+1) x n_total");
-        check(cmpc_di_rounds_set_traj(g_h[h], mxGetPr(T)), "cmpc_di_rounds_set_traj");
-        return;
-    }
-    mwSize d[3] = {2, (mwSize)(N + 1), (mwSize)g_hB[h]};
-    mxArray* T = mxCreateNumericArray(3, d, mxDOUBLE_CLASS, mxREAL);
-    check(cmpc_di_rounds_get_traj(g_h[h], mxGetPr(T)), "cmpc_di_rounds_get_traj");
-    plhs[0] = T;
-}
-
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char cmd[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], cmd, sizeof cmd) != 0)
-        mexErrMsgIdAndTxt("cmpc:di:args", "usage: cmpc_di('rounds_create' | 'rounds_step' | 'rounds_read' | "
-                                          "'rounds_history' | 'rounds_log_enable' | 'rounds_log' | 'rounds_get_traj' | 'rounds_set_traj' | "
-                                          "'rounds_destroy' | 'comm_id' | 'comm_init', ...)");
+        ARGS_ERROR("usage: cmpc_di('rounds_create' | 'rounds_step' | 'rounds_read' | "
+                   "'rounds_history' | 'rounds_log_enable' | 'rounds_log' | 'rounds_get_traj' | 'rounds_set_traj' | "
+                   "'rounds_destroy' | 'comm_id' | 'comm_init', ...)");
     if (!strcmp(cmd, "rounds_create")) {
-        rounds_create(nlhs, plhs, nrhs, prhs);
+        rounds_create(plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_step")) {
-        rounds_step(nlhs, plhs, nrhs, prhs);
+        rounds_step(plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_read")) {
         rounds_read(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_history")) {
         rounds_history(nlhs, plhs, nrhs, prhs);
-    } else if (!strcmp(cmd, "rounds_log_enable")) {
-        rounds_log_enable(nlhs, plhs, nrhs, prhs);
-    } else if (!strcmp(cmd, "rounds_log")) {
-        rounds_log(nlhs, plhs, nrhs, prhs);
-    } else if (!strcmp(cmd, "rounds_get_traj") || !strcmp(cmd, "rounds_set_traj")) {
-        rounds_traj(nlhs, plhs, nrhs, prhs, cmd[7] == 's');
-    } else if (!strcmp(cmd, "rounds_destroy")) {
-        if (nrhs != 2) mexErrMsgIdAndTxt("cmpc:di:args", "usage: cmpc_di('rounds_destroy', h)");
-        const int h = handle_of(prhs[1]);
-        cmpc_di_rounds_destroy(g_h[h]);
-        g_h[h] = NULL;
-    } else if (!strcmp(cmd, "comm_id")) {
-        unsigned char id[CMPC_COMM_ID_BYTES];
-        if (cmpc_comm_id(id) != CMPC_OK) mexErrMsgIdAndTxt("cmpc:device", "cmpc_comm_id failed");
-        plhs[0] = mxCreateDoubleMatrix(1, CMPC_COMM_ID_BYTES, mxREAL);
-        for (int i = 0; i < CMPC_COMM_ID_BYTES; ++i) mxGetPr(plhs[0])[i] = id[i];
-    } else if (!strcmp(cmd, "comm_init")) {
-        if (nrhs != 4 || mxGetNumberOfElements(prhs[3]) != CMPC_COMM_ID_BYTES)
-            mexErrMsgIdAndTxt("cmpc:di:args", "usage: cmpc_di('comm_init', nranks, rank, id)");
-        unsigned char id[CMPC_COMM_ID_BYTES];
-        for (int i = 0; i < CMPC_COMM_ID_BYTES; ++i) id[i] = (unsigned char)mxGetPr(prhs[3])[i];
-        ensure_ctx();
-        check(cmpc_comm_init(g_ctx, (int)mxGetScalar(prhs[1]), (int)mxGetScalar(prhs[2]), id), "cmpc_comm_init");
-    } else {
-        mexErrMsgIdAndTxt("cmpc:di:args", "unknown command '%s'", cmd);
+    } else if (!shared_command(cmd, plhs, nrhs, prhs)) {
+        ARGS_ERROR("unknown command '%s'", cmd);
     }
 }

@@ -48,62 +48,9 @@
 #include "cmpc.h"
 #include "mex.h"
 
-#define MAX_HANDLES 64
-
-static cmpc_ctx* g_ctx = NULL;
-static cmpc_lpv_rounds* g_h[MAX_HANDLES];
-static int g_hN[MAX_HANDLES], g_hB[MAX_HANDLES], g_hnb[MAX_HANDLES], g_hT[MAX_HANDLES];
-static int g_hlog[MAX_HANDLES]; /* CMPC_LOG_* flags of rounds_log_enable */
-
-static void cleanup(void) {
-    for (int i = 0; i < MAX_HANDLES; ++i)
-        if (g_h[i]) {
-            cmpc_lpv_rounds_destroy(g_h[i]);
-            g_h[i] = NULL;
-        }
-    if (g_ctx) cmpc_destroy(g_ctx);
-    g_ctx = NULL;
-}
-
-static void ensure_ctx(void) {
-    if (!g_ctx) {
-        if (cmpc_create(&g_ctx, 0) != CMPC_OK) {
-            g_ctx = NULL;
-            mexErrMsgIdAndTxt("cmpc:device", "cmpc_lpv: no usable MI355X (gfx950) device");
-        }
-        mexAtExit(cleanup);
-    }
-}
-
-static void check(int rc, const char* what) {
-    if (rc != CMPC_OK) mexErrMsgIdAndTxt("cmpc:solve", "%s failed (%d): %s", what, rc, cmpc_last_error(g_ctx));
-}
-
-static const mxArray* field(const mxArray* S, const char* name, size_t numel, int required) {
-    const mxArray* v = mxGetField(S, 0, name);
-    if (!v || mxIsEmpty(v)) {
-        if (required) mexErrMsgIdAndTxt("cmpc:lpv:args", "field %s is required", name);
-        return NULL;
-    }
-    if (!mxIsDouble(v) || mxIsComplex(v) || mxIsSparse(v))
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "field %s must be a full real double array", name);
-    if (numel && mxGetNumberOfElements(v) != numel)
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "field %s has %zu elements, expected %zu", name, mxGetNumberOfElements(v),
-                          numel);
-    return v;
-}
-
-static double scalar(const mxArray* S, const char* name) { return mxGetScalar(field(S, name, 1, 1)); }
-
-static double scalar_or(const mxArray* S, const char* name, double dflt) {
-    const mxArray* v = field(S, name, 1, 0);
-    return v ? mxGetScalar(v) : dflt;
-}
-
-static const mxArray* require_struct(const mxArray* a, const char* what) {
-    if (!a || !mxIsStruct(a)) mexErrMsgIdAndTxt("cmpc:lpv:args", "%s must be a struct", what);
-    return a;
-}
+#define CMPC_MEX_FAMILY cmpc_lpv
+#define CMPC_MEX_ARGS "cmpc:lpv:args"
+#include "cmpc_mex_rounds.h"
 
 /* P -> parameters, track, horizon, options */
 typedef struct {
@@ -141,7 +88,7 @@ static void read_params(const mxArray* P, lpv_setup* s) {
     } else if (nq == 9) {  /* the reference passes Qs as a 3x3 (diagonal) matrix */
         for (int j = 0; j < 3; ++j) p->Qs[j] = mxGetPr(qs)[j * 4];
     } else {
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "Qs must be 3x1 or 3x3 (diagonal)");
+        ARGS_ERROR("Qs must be 3x1 or 3x3 (diagonal)");
     }
     s->N = (int)scalar(P, "N");
     const mxArray* T = require_struct(mxGetField(P, 0, "track"), "P.track");
@@ -169,17 +116,17 @@ static void read_data(const mxArray* D, int N, lpv_batch* b) {
     require_struct(D, "D");
     const mxArray* x0 = field(D, "x0", 0, 1);
     const size_t B = mxGetNumberOfElements(x0) / 9;
-    if (B * 9 != mxGetNumberOfElements(x0) || B == 0) mexErrMsgIdAndTxt("cmpc:lpv:args", "x0 must be 9 x B");
+    if (B * 9 != mxGetNumberOfElements(x0) || B == 0) ARGS_ERROR("x0 must be 9 x B");
     const mxArray* xl = field(D, "x_last", 0, 1);
     const size_t rows = mxGetNumberOfElements(xl) / (9 * B);
     if (rows * 9 * B != mxGetNumberOfElements(xl) || (rows != (size_t)N && rows != (size_t)N + 1))
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "x_last must be 9 x (N or N+1) x B");
+        ARGS_ERROR("x_last must be 9 x (N or N+1) x B");
     const mxArray* xa = field(D, "x_agents", 0, 0);
     size_t nb = 0;
     if (xa) {
         nb = mxGetNumberOfElements(xa) / (2 * (size_t)(N + 1) * B);
         if (nb * 2 * (N + 1) * B != mxGetNumberOfElements(xa) || nb == 0)
-            mexErrMsgIdAndTxt("cmpc:lpv:args", "x_agents must be 2 x nb x (N+1) x B");
+            ARGS_ERROR("x_agents must be 2 x nb x (N+1) x B");
     }
     b->B = (int)B;
     b->nb = (int)nb;
@@ -193,18 +140,13 @@ static void read_data(const mxArray* D, int N, lpv_batch* b) {
     b->d.pose = mxGetPr(field(D, "pose", 2 * (size_t)(N + 1) * B, 1));
 }
 
-static mxArray* dmat3(size_t a, size_t b, size_t c) {
-    mwSize d[3] = {(mwSize)a, (mwSize)b, (mwSize)c};
-    return mxCreateNumericArray(3, d, mxDOUBLE_CLASS, mxREAL);
-}
-
 static mxArray* planes_array(int N, int nb, int B) {
     mwSize d[4] = {(mwSize)(nb ? nb : 1), 3, (mwSize)N, (mwSize)B};
     return mxCreateNumericArray(4, d, mxDOUBLE_CLASS, mxREAL);
 }
 
 static void solve(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    if (nrhs != 3) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('solve', P, D)");
+    if (nrhs != 3) ARGS_ERROR("usage: cmpc_lpv('solve', P, D)");
     lpv_setup s;
     read_params(prhs[1], &s);
     lpv_batch b;
@@ -228,10 +170,8 @@ static void solve(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     const int rc = cmpc_solve_lpv_batch(g_ctx, &s.prm, &s.track, &dims, &b.d, &out, &s.opts);
     if (zero_uo) mxFree(zero_uo);
     check(rc, "cmpc_solve_lpv_batch");
-    for (int i = 0; i < b.B; ++i) {
-        mxGetPr(IT)[i] = iters[i];
-        mxGetPr(ST)[i] = status[i];
-    }
+    widen(IT, iters, b.B);
+    widen(ST, status, b.B);
     mxFree(iters);
     mxFree(status);
     plhs[0] = Z;
@@ -241,72 +181,48 @@ static void solve(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nlhs > 4) plhs[4] = PL;
 }
 
-static int handle_of(const mxArray* a) {
-    if (!a || !mxIsDouble(a) || mxGetNumberOfElements(a) != 1) mexErrMsgIdAndTxt("cmpc:lpv:args", "bad rounds handle");
-    const int h = (int)mxGetScalar(a) - 1;
-    if (h < 0 || h >= MAX_HANDLES || !g_h[h]) mexErrMsgIdAndTxt("cmpc:lpv:args", "bad rounds handle");
-    return h;
-}
-
-static void rounds_create(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    if (nrhs != 4) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: h = cmpc_lpv('rounds_create', P, D, S)");
+static void rounds_create(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs != 4) ARGS_ERROR("usage: h = cmpc_lpv('rounds_create', P, D, S)");
     lpv_setup s;
     read_params(prhs[1], &s);
     lpv_batch b;
     read_data(prhs[2], s.N, &b);
-    if (b.rows != s.N + 1) mexErrMsgIdAndTxt("cmpc:lpv:args", "rounds start from Last_xPredicted with N+1 rows");
+    if (b.rows != s.N + 1) ARGS_ERROR("rounds start from Last_xPredicted with N+1 rows");
     const mxArray* S = require_struct(prhs[3], "S");
     const int n_total = (int)scalar_or(S, "n_total", (double)b.B);
     const int self_offset = (int)scalar_or(S, "self_offset", 0.0);
     const mxArray* nbr = field(S, "nbr", 0, b.nb > 0);
     int nb = nbr ? (int)(mxGetNumberOfElements(nbr) / (size_t)b.B) : 0;
-    if (nbr && (size_t)nb * b.B != mxGetNumberOfElements(nbr)) mexErrMsgIdAndTxt("cmpc:lpv:args", "nbr must be nb x B");
+    if (nbr && (size_t)nb * b.B != mxGetNumberOfElements(nbr)) ARGS_ERROR("nbr must be nb x B");
     const mxArray* traj = field(S, "traj", 2 * (size_t)(s.N + 1) * n_total, 0);
-    int* inbr = (int*)mxCalloc((size_t)(nb ? nb : 1) * b.B, sizeof(int));
-    for (size_t i = 0; nbr && i < (size_t)nb * b.B; ++i) inbr[i] = (int)mxGetPr(nbr)[i];
     const int flags = (scalar_or(S, "host_exchange", 0.0) != 0.0 ? CMPC_ROUNDS_HOST_EXCHANGE : 0) |
                       (scalar_or(S, "halt", 1.0) != 0.0 ? 0 : CMPC_ROUNDS_NO_HALT);
+    const int slot = free_slot();
+    int* inbr = nbr_ints(nbr, (size_t)nb * b.B);
     cmpc_lpv_rounds_dims dims = {n_total, b.B, self_offset, s.N, nb, flags};
     cmpc_lpv_rounds_init init = {b.d.x0, b.d.x_last, b.d.u_last, b.d.u_old, inbr, traj ? mxGetPr(traj) : NULL};
-    int slot = -1;
-    for (int i = 0; i < MAX_HANDLES && slot < 0; ++i)
-        if (!g_h[i]) slot = i;
-    if (slot < 0) {
-        mxFree(inbr);
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "too many open rounds handles (%d)", MAX_HANDLES);
-    }
     ensure_ctx();
-    const int rc = cmpc_lpv_rounds_create(g_ctx, &s.prm, &s.track, &dims, &init, &s.opts, &g_h[slot]);
+    const int rc = cmpc_lpv_rounds_create(g_ctx, &s.prm, &s.track, &dims, &init, &s.opts, &g_tab[slot].h);
     mxFree(inbr);
     check(rc, "cmpc_lpv_rounds_create");
-    g_hN[slot] = s.N;
-    g_hB[slot] = b.B;
-    g_hnb[slot] = nb;
-    g_hT[slot] = n_total;
-    g_hlog[slot] = 0;
-    plhs[0] = mxCreateDoubleMatrix(1, 1, mxREAL);
-    mxGetPr(plhs[0])[0] = slot + 1;
+    g_tab[slot] = (rounds_slot){g_tab[slot].h, s.N, b.B, nb, n_total, 9, 2, 0};
+    plhs[0] = scalar_out(slot + 1);
 }
 
 static void rounds_step(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    if (nrhs != 3) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: [done, infeasible] = cmpc_lpv('rounds_step', h, k)");
-    const int h = handle_of(prhs[1]);
+    if (nrhs != 3) ARGS_ERROR("usage: [done, infeasible] = cmpc_lpv('rounds_step', h, k)");
+    const rounds_slot* t = handle_of(prhs[1]);
     const int k = (int)mxGetScalar(prhs[2]);
     int done = 0, bad = 0;
-    check(cmpc_lpv_rounds_step(g_h[h], k, &done, &bad), "cmpc_lpv_rounds_step");
-    plhs[0] = mxCreateDoubleMatrix(1, 1, mxREAL);
-    mxGetPr(plhs[0])[0] = done;
-    if (nlhs > 1) {
-        plhs[1] = mxCreateDoubleMatrix(1, 1, mxREAL);
-        mxGetPr(plhs[1])[0] = bad;
-    }
+    check(cmpc_lpv_rounds_step(t->h, k, &done, &bad), "cmpc_lpv_rounds_step");
+    plhs[0] = scalar_out(done);
+    if (nlhs > 1) plhs[1] = scalar_out(bad);
 }
 
 static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    if (nrhs != 2) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: [z, status, kkt, iters, x0, planes] = cmpc_lpv('rounds_read', h)");
-    const int h = handle_of(prhs[1]);
-    const int N = g_hN[h], B = g_hB[h], nb = g_hnb[h];
+    if (nrhs != 2) ARGS_ERROR("usage: [z, status, kkt, iters, x0, planes] = cmpc_lpv('rounds_read', h)");
+    const rounds_slot* t = handle_of(prhs[1]);
+    const int N = t->N, B = t->B, nb = t->nb;
     const size_t nz = 12 * (size_t)(N + 1) + 4 * (size_t)N;
     mxArray* Z = mxCreateDoubleMatrix(nz, B, mxREAL);
     mxArray* ST = mxCreateDoubleMatrix(1, B, mxREAL);
@@ -317,12 +233,11 @@ static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     int* iters = (int*)mxCalloc(B, sizeof(int));
     int* status = (int*)mxCalloc(B, sizeof(int));
     cmpc_lpv_rounds_out o = {mxGetPr(Z), mxGetPr(KK), iters, status, mxGetPr(X0), nb ? mxGetPr(PL) : NULL};
-    const int rc = cmpc_lpv_rounds_read(g_h[h], &o);
-    if (rc == CMPC_OK)
-        for (int i = 0; i < B; ++i) {
-            mxGetPr(IT)[i] = iters[i];
-            mxGetPr(ST)[i] = status[i];
-        }
+    const int rc = cmpc_lpv_rounds_read(t->h, &o);
+    if (rc == CMPC_OK) {
+        widen(IT, iters, B);
+        widen(ST, status, B);
+    }
     mxFree(iters);
     mxFree(status);
     check(rc, "cmpc_lpv_rounds_read");
@@ -334,118 +249,22 @@ static void rounds_read(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     if (nlhs > 5) plhs[5] = PL;
 }
 
-static void rounds_log_enable(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    (void)plhs;
-    if (nrhs != 3 && nrhs != 4)
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('rounds_log_enable', h, capacity [, flags])");
-    const int h = handle_of(prhs[1]);
-    const int flags = nrhs > 3 ? (int)mxGetScalar(prhs[3]) : 0;
-    check(cmpc_lpv_rounds_log_enable(g_h[h], (int)mxGetScalar(prhs[2]), flags), "cmpc_lpv_rounds_log_enable");
-    g_hlog[h] = flags;
-}
-
-static void rounds_log(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    if (nrhs != 2 && nrhs != 4) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: L = cmpc_lpv('rounds_log', h [, first, count])");
-    const int h = handle_of(prhs[1]);
-    const int B = g_hB[h], sep = g_hlog[h] & CMPC_LOG_SEPARATION;
-    int first = 0, count = 0;
-    if (nrhs == 2) {
-        check(cmpc_lpv_rounds_log_range(g_h[h], &first, &count), "cmpc_lpv_rounds_log_range");
-    } else {
-        first = (int)mxGetScalar(prhs[2]);
-        count = (int)mxGetScalar(prhs[3]);
-    }
-    if (first < 0 || count < 0) mexErrMsgIdAndTxt("cmpc:lpv:args", "first and count must be >= 0");
-    const size_t n = (size_t)B * count;
-    mxArray* XS = dmat3(9, B, count);
-    mxArray* US = dmat3(2, B, count);
-    mxArray* LA = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* KK = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* IT = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* ST = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* S2 = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* NR = mxCreateDoubleMatrix(B, count, mxREAL);
-    mxArray* MS = mxCreateDoubleMatrix(count, 1, mxREAL);
-    int* ibuf = (int*)mxCalloc(3 * (n ? n : 1), sizeof(int));
-    int *iters = ibuf, *status = ibuf + (n ? n : 1), *nearest = status + (n ? n : 1);
-    const cmpc_rounds_log o = {mxGetPr(XS), mxGetPr(US), mxGetPr(LA), mxGetPr(KK), iters, status,
-                               sep ? mxGetPr(S2) : NULL, sep ? nearest : NULL, mxGetPr(MS)};
-    const int rc = cmpc_lpv_rounds_log_read(g_h[h], first, count, &o);
-    if (rc == CMPC_OK)
-        for (size_t i = 0; i < n; ++i) {
-            mxGetPr(IT)[i] = iters[i];
-            mxGetPr(ST)[i] = status[i];
-            if (sep) mxGetPr(NR)[i] = nearest[i];
-        }
-    mxFree(ibuf);
-    check(rc, "cmpc_lpv_rounds_log_read");
-    const char* names[] = {"first", "state", "u", "look_ahead", "kkt", "iters", "status", "solve_ms", "sep2", "nearest"};
-    mxArray* L = mxCreateStructMatrix(1, 1, sep ? 10 : 8, names);
-    mxArray* F = mxCreateDoubleMatrix(1, 1, mxREAL);
-    mxGetPr(F)[0] = first;
-    mxArray* vals[] = {F, XS, US, LA, KK, IT, ST, MS, S2, NR};
-    for (int i = 0; i < (sep ? 10 : 8); ++i) mxSetField(L, 0, names[i], vals[i]);
-    plhs[0] = L;
-}
-
-static void rounds_traj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int set) {
-    (void)nlhs;
-    if (nrhs != (set ? 3 : 2)) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: rounds_get_traj(h) / rounds_set_traj(h, T)");
-    const int h = handle_of(prhs[1]);
-    const int N = g_hN[h];
-    if (set) {
-        const mxArray* T = prhs[2];
-        if (!mxIsDouble(T) || mxGetNumberOfElements(T) != 2 * (size_t)(N + 1) * g_hT[h])
-            mexErrMsgIdAndTxt("cmpc:lpv:args", "T must be 2 x (N+1) x n_total");
-        check(cmpc_lpv_rounds_set_traj(g_h[h], mxGetPr(T)), "cmpc_lpv_rounds_set_traj");
-        return;
-    }
-    mxArray* T = dmat3(2, N + 1, g_hB[h]);
-    check(cmpc_lpv_rounds_get_traj(g_h[h], mxGetPr(T)), "cmpc_lpv_rounds_get_traj");
-    plhs[0] = T;
-}
-
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char cmd[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], cmd, sizeof cmd) != 0)
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('solve' | 'rounds_create' | 'rounds_step' | 'rounds_read' | "
-                                           "'rounds_log_enable' | 'rounds_log' | "
-                                           "'rounds_get_traj' | 'rounds_set_traj' | 'rounds_destroy' | 'comm_id' | "
-                                           "'comm_init', ...)");
+        ARGS_ERROR("usage: cmpc_lpv('solve' | 'rounds_create' | 'rounds_step' | 'rounds_read' | "
+                   "'rounds_log_enable' | 'rounds_log' | "
+                   "'rounds_get_traj' | 'rounds_set_traj' | 'rounds_destroy' | 'comm_id' | "
+                   "'comm_init', ...)");
     if (!strcmp(cmd, "solve")) {
         solve(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_create")) {
-        rounds_create(nlhs, plhs, nrhs, prhs);
+        rounds_create(plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_step")) {
         rounds_step(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rounds_read")) {
         rounds_read(nlhs, plhs, nrhs, prhs);
-    } else if (!strcmp(cmd, "rounds_log_enable")) {
-        rounds_log_enable(nlhs, plhs, nrhs, prhs);
-    } else if (!strcmp(cmd, "rounds_log")) {
-        rounds_log(nlhs, plhs, nrhs, prhs);
-    } else if (!strcmp(cmd, "rounds_get_traj") || !strcmp(cmd, "rounds_set_traj")) {
-        rounds_traj(nlhs, plhs, nrhs, prhs, cmd[7] == 's');
-    } else if (!strcmp(cmd, "rounds_destroy")) {
-        if (nrhs != 2) mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('rounds_destroy', h)");
-        const int h = handle_of(prhs[1]);
-        cmpc_lpv_rounds_destroy(g_h[h]);
-        g_h[h] = NULL;
-    } else if (!strcmp(cmd, "comm_id")) {
-        unsigned char id[CMPC_COMM_ID_BYTES];
-        if (cmpc_comm_id(id) != CMPC_OK) mexErrMsgIdAndTxt("cmpc:device", "cmpc_comm_id failed");
-        plhs[0] = mxCreateDoubleMatrix(1, CMPC_COMM_ID_BYTES, mxREAL);
-        for (int i = 0; i < CMPC_COMM_ID_BYTES; ++i) mxGetPr(plhs[0])[i] = id[i];
-    } else if (!strcmp(cmd, "comm_init")) {
-        if (nrhs != 4 || mxGetNumberOfElements(prhs[3]) != CMPC_COMM_ID_BYTES)
-            mexErrMsgIdAndTxt("cmpc:lpv:args", "usage: cmpc_lpv('comm_init', nranks, rank, id)");
-        unsigned char id[CMPC_COMM_ID_BYTES];
-        for (int i = 0; i < CMPC_COMM_ID_BYTES; ++i) id[i] = (unsigned char)mxGetPr(prhs[3])[i];
-        ensure_ctx();
-        check(cmpc_comm_init(g_ctx, (int)mxGetScalar(prhs[1]), (int)mxGetScalar(prhs[2]), id), "cmpc_comm_init");
-    } else {
-        mexErrMsgIdAndTxt("cmpc:lpv:args", "unknown command '%s'", cmd);
+    } else if (!shared_command(cmd, plhs, nrhs, prhs)) {
+        ARGS_ERROR("unknown command '%s'", cmd);
     }
 }

@@ -183,3 +183,76 @@ def test_lpv_rounds_at_scale_against_c_restatement(gpu_ctx):
     assert dg["count"] <= 0.005 * smp["checked"], dg
     if dg["count"]:
         assert dg["max_ref_kkt_gpu"] <= 1e-6 and dg["max_obj_gap_rel"] <= 1e-10, dg
+
+
+def _raw_lpv_create(ctx, bp, args, kw, dims=None, init=None, track=None, opts=None, null=()):
+    """cmpc_lpv_rounds_create on a `_case` with fields replaced; returns (rc, handle)."""
+    import ctypes as ct
+
+    from cmpc import _lib as L
+
+    x0, x_last, u_last, nbr = args
+    n = x0.shape[0]
+    d = dict(n_total=n, batch=n, self_offset=0, N=bp.N, nb=nbr.shape[1], flags=0)
+    d.update(dims or {})
+    cd = L.cmpc_lpv_rounds_dims(*[d[k] for k in ("n_total", "batch", "self_offset", "N", "nb", "flags")])
+    a = dict(x0=L.f64(x0), x_last=L.f64(x_last), u_last=L.f64(u_last), u_old=L.f64(kw["u_old"]), nbr=L.i32(nbr),
+             traj=L.f64(kw["traj"]))
+    a.update(init or {})
+    ci = L.cmpc_lpv_rounds_init(*[None if k in null else (L.iptr(a[k]) if k == "nbr" else L.dptr(a[k]))
+                                  for k in ("x0", "x_last", "u_last", "u_old", "nbr", "traj")])
+    t = bp.track
+    ctk = L.cmpc_track(t.nseg if track is None else track, t.s0, t.len, t.curv, t.half_width)
+    co = L.opts(bp.opts.tol, bp.opts.max_iter, bp.opts.flags if opts is None else opts)
+    h = ct.c_void_p()
+    ref = lambda name, v: None if name in null else ct.byref(v)  # noqa: E731
+    rc = ctx.lib.cmpc_lpv_rounds_create(ctx.h, ref("prm", bp.prm), ref("track", ctk), ref("dims", cd), ref("init", ci),
+                                        ref("opts", co), None if "out" in null else ct.byref(h))
+    return rc, h
+
+
+def test_lpv_rounds_create_argument_errors(gpu_ctx):
+    """The argument checks of cmpc_lpv_rounds_create and the NULL-handle calls, on the smallest captured case
+    (2 agents, N = 10, one neighbour each); no solver launch."""
+    from cmpc import _lib as L
+
+    bp, args, kw, _ = _case("lpv_n10_a2", gpu_ctx)
+    lib = gpu_ctx.lib
+    host_x = L.CMPC_ROUNDS_HOST_EXCHANGE
+    good = [dict(null=("opts",)),                                    # opts may be NULL
+            dict(null=("traj",)),                                    # unsharded: taken from x_last[:, :, 7:9]
+            dict(null=("u_old",)),                                   # zeros
+            dict(dims=dict(batch=1, self_offset=1, flags=host_x))]   # a valid shard
+    for case in good:
+        rc, h = _raw_lpv_create(gpu_ctx, bp, args, kw, **case)
+        assert rc == L.CMPC_OK and h.value, case
+        assert lib.cmpc_lpv_rounds_destroy(h) == L.CMPC_OK
+    far = args[3].copy()
+    far[1, 0] = 2
+    neg = args[3].copy()
+    neg[0, 0] = -1
+    bad = [dict(null=("prm",)), dict(null=("track",)), dict(null=("dims",)), dict(null=("init",)), dict(null=("out",)),
+           dict(null=("x0",)), dict(null=("x_last",)), dict(null=("u_last",)), dict(null=("nbr",)),
+           dict(dims=dict(batch=0)), dict(dims=dict(batch=3)), dict(dims=dict(self_offset=-1)),
+           dict(dims=dict(batch=1, self_offset=2, flags=host_x)),
+           dict(dims=dict(N=0)), dict(dims=dict(nb=-1)), dict(dims=dict(nb=13)),
+           dict(init=dict(nbr=far)), dict(init=dict(nbr=neg)),
+           dict(dims=dict(batch=1)),                                 # sharded: no communicator, no host exchange
+           dict(dims=dict(batch=1, flags=host_x), null=("traj",)),   # sharded: the exchange buffer is required
+           dict(dims=dict(flags=L.CMPC_ROUNDS_LPT)),                 # the synthetic family's handle only
+           dict(dims=dict(flags=16)), dict(dims=dict(flags=-1)),
+           dict(dims=dict(nb=2, flags=L.CMPC_ROUNDS_RESELECT), init=dict(nbr=np.zeros((2, 2), np.int32))),
+           dict(opts=1 << 20)]
+    for case in bad:
+        rc, h = _raw_lpv_create(gpu_ctx, bp, args, kw, **case)
+        assert rc == L.CMPC_ERR_ARG and not h.value, case
+        assert lib.cmpc_last_error(gpu_ctx.h), case
+    for nseg in (0, 33):
+        rc, h = _raw_lpv_create(gpu_ctx, bp, args, kw, track=nseg)
+        assert rc == L.CMPC_ERR_UNSUPPORTED and not h.value, nseg
+    for fn, a in ((lib.cmpc_lpv_rounds_step, (None, 1, None, None)), (lib.cmpc_lpv_rounds_read, (None, None)),
+                  (lib.cmpc_lpv_rounds_get_traj, (None, None)), (lib.cmpc_lpv_rounds_set_traj, (None, None)),
+                  (lib.cmpc_lpv_rounds_log_enable, (None, 1, 0)), (lib.cmpc_lpv_rounds_log_range, (None, None, None)),
+                  (lib.cmpc_lpv_rounds_log_read, (None, 0, 0, None))):
+        assert fn(*a) == L.CMPC_ERR_ARG
+    assert lib.cmpc_lpv_rounds_destroy(None) == L.CMPC_OK
