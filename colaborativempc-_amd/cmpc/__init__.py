@@ -5,6 +5,7 @@ include/cmpc.h).  This package is the host-side mirror of the reference's
 planner interface (MarcFacerias/ColaborativeMPC-, planner/lib/plan_lib) plus the
 round driver and synthetic workloads.  There is no CPU solve path here.
 """
+from . import duals
 from ._lib import (CMPC_MAX_ITER_REACHED, CMPC_SOLVED, CMPC_SOLVED_INACCURATE, CMPC_UNSOLVED, CmpcError,
                    Context, default_context, load)
 from .planner import PlannerLPV, PlannerLPVBatch, feasible_of, unpack
@@ -13,7 +14,7 @@ from .rounds import DIRoundsHandle, log_round_dev, order_by_iters_dev, select_ne
 from .scenarios import log_row, order_by_iters, select_neighbours
 from .solver import nz_of, selftest_fma_bcast, selftest_mfma, solve_mpc, solve_mpc_dev
 
-__all__ = ["log_row", "log_round_dev", "select_neighbours", "select_neighbours_dev", "order_by_iters", "order_by_iters_dev", "DIRoundsHandle",
+__all__ = ["duals", "log_row", "log_round_dev", "select_neighbours", "select_neighbours_dev", "order_by_iters", "order_by_iters_dev", "DIRoundsHandle",
            "Context", "CmpcError", "default_context", "load", "PlannerLPV", "PlannerLPVBatch", "feasible_of",
            "unpack", "quadprog", "osqp_solve_qp", "osqp_solve_qp_batch", "solve_mpc", "solve_mpc_dev", "nz_of", "selftest_mfma", "selftest_fma_bcast", "CMPC_SOLVED",
            "CMPC_SOLVED_INACCURATE", "CMPC_MAX_ITER_REACHED", "CMPC_UNSOLVED"]

@@ -78,6 +78,10 @@ class cmpc_mpc_out(ct.Structure):
     _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP)]
 
 
+class cmpc_mpc_duals(ct.Structure):
+    _fields_ = [("y", _DP), ("dua_res", _DP)]
+
+
 class cmpc_lpv_params(ct.Structure):
     _fields_ = [(k, ct.c_double) for k in ("lf", "lr", "m", "I", "Cf", "Cr", "mu", "vx_ref", "min_dist",
                                            "max_vel", "min_vel", "max_rs", "max_ls", "max_ac", "max_dc",
@@ -209,6 +213,15 @@ SIGNATURES = {
     "cmpc_solve_mpc_batch_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
                                             ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out),
                                             ct.POINTER(cmpc_opts), ct.c_void_p]),
+    "cmpc_solve_mpc_batch_duals": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                              ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out),
+                                              ct.POINTER(cmpc_mpc_duals), ct.POINTER(cmpc_opts)]),
+    "cmpc_solve_mpc_batch_duals_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims),
+                                                  ct.POINTER(cmpc_mpc_weights), ct.POINTER(cmpc_mpc_data),
+                                                  ct.POINTER(cmpc_mpc_out), ct.POINTER(cmpc_mpc_duals),
+                                                  ct.POINTER(cmpc_opts), ct.c_void_p]),
+    "cmpc_mpc_duals_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                      ct.POINTER(cmpc_mpc_data), _DP, _DP, ct.POINTER(cmpc_mpc_duals), ct.c_void_p]),
     "cmpc_solve_lpv_batch": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lpv_params), ct.POINTER(cmpc_track),
                                         ct.POINTER(cmpc_lpv_dims), ct.POINTER(cmpc_lpv_data),
                                         ct.POINTER(cmpc_lpv_out), ct.POINTER(cmpc_opts)]),

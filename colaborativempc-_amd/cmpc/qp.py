@@ -96,9 +96,10 @@ def quadprog(H, f, A=None, b=None, Aeq=None, beq=None, lb=None, ub=None, ctx=Non
     return res
 
 
-def _osqp_result(x, status_val, text, iters, obj, kkt, pri_res, path):
-    res = SimpleNamespace(x=x, y=None, info=SimpleNamespace(status_val=status_val, status=text, iter=iters,
-                                                           obj_val=obj, kkt=kkt, pri_res=pri_res, solver=path))
+def _osqp_result(x, y, status_val, text, iters, obj, kkt, pri_res, dua_res, path):
+    res = SimpleNamespace(x=x, y=y, info=SimpleNamespace(status_val=status_val, status=text, iter=iters,
+                                                         obj_val=obj, kkt=kkt, pri_res=pri_res, dua_res=dua_res,
+                                                         solver=path))
     feasible = 1 if status_val in (1, 2, -2) else 0   # LPV_Planner.py:243-249
     if status_val != 1:
         print("OSQP exited with status '%s'" % text)
@@ -113,6 +114,17 @@ def _pri_res(z, G, h, A, b):
     if G is not None and h is not None:
         r = max(r, float(np.maximum(G @ z - np.asarray(h, float).ravel(), 0.0).max(initial=0.0)))
     return r
+
+
+def _dua_res(x, y, P, q, G, A):
+    """Reference-form dual residual ||P x + q + [G; A]'y||_inf (OSQP's dua_res, unscaled)."""
+    r = P @ x + np.asarray(q, float).ravel()
+    mi = 0 if G is None else G.shape[0]
+    if mi:
+        r = r + G.T @ y[:mi]
+    if A is not None and A.shape[0]:
+        r = r + A.T @ y[mi:]
+    return float(np.abs(np.asarray(r).ravel()).max(initial=0.0))
 
 
 def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True):
@@ -135,13 +147,16 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
         batch = St.stack([recs[i] for i in idx])
         # CMPC_FLAG_RESCUE, as PlannerLPV / PlannerLPVBatch: a condensed factorisation breakdown
         # continues on the stage-wise kernel instead of returning CMPC_UNSOLVED (OSQP's -10)
-        z, kkt, it, st = solve_mpc(batch, ctx, tol=tol, max_iter=max_iter, rescue=True, polish=True)
+        # res.y: the dual solution in OSQP's order [G rows; A rows] (cmpc.duals; NaN where the solver's exit
+        # holds no multipliers of the iterate it returns, never at status 1)
+        z, kkt, it, st, y, dua = solve_mpc(batch, ctx, tol=tol, max_iter=max_iter, rescue=True, polish=True,
+                                           duals=True)
         for a, i in enumerate(idx):
             P, q, G, h, A, b = qps[i][:6]
             x = z[a]
             obj = float(0.5 * x @ (P @ x) + np.asarray(q, float) @ x)
-            out[i] = _osqp_result(x, int(st[a]), L.STATUS_TEXT.get(int(st[a]), "unsolved"), int(it[a]), obj,
-                                  float(kkt[a]), _pri_res(x, G, h, A, b), "structured")
+            out[i] = _osqp_result(x, y[a], int(st[a]), L.STATUS_TEXT.get(int(st[a]), "unsolved"), int(it[a]), obj,
+                                  float(kkt[a]), _pri_res(x, G, h, A, b), float(dua[a]), "structured")
     for i, p in enumerate(recs):
         if p is not None:
             continue
@@ -151,8 +166,10 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
         x = r["x"]
         Gs = None if G is None else (G if hasattr(G, "toarray") else np.asarray(G, float))
         As = None if A is None else (A if hasattr(A, "toarray") else np.asarray(A, float))
-        out[i] = _osqp_result(x, sv, text, int(r["iterations"]), float(r["fval"]), float(r["residual"]),
-                              _pri_res(x, Gs, h, As, b), "dense")
+        # quadprog's multipliers carry OSQP's signs (tests/test_qp_contract_gpu.py): y = [ineqlin; eqlin]
+        y = np.concatenate([r["lambda"]["ineqlin"], r["lambda"]["eqlin"]])
+        out[i] = _osqp_result(x, y, sv, text, int(r["iterations"]), float(r["fval"]), float(r["residual"]),
+                              _pri_res(x, Gs, h, As, b), _dua_res(x, y, P, q, Gs, As), "dense")
     return out
 
 

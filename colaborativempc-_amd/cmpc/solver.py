@@ -78,7 +78,7 @@ def plan(shared, batch=1, fp32=False, riccati=False, generic=False, lane=False, 
 
 
 def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, generic=False, rescue=False,
-              stamps=None, lane=False, polish=False):
+              stamps=None, lane=False, polish=False, duals=False):
     """Solve a batch of structured agent-QPs on the GPU (host arrays in/out).
     ``fp32``: the fp32 path (BASELINE cfg5): fp32 Riccati factorisation and Newton recursions with
     fp64 iterates — the Riccati kernel's fp32 mode where it is instantiated (nx, nu, mc = 6, 3, 6),
@@ -91,9 +91,13 @@ def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, g
     the stage-wise Riccati kernel; PlannerLPV's default);
     ``polish``: CMPC_FLAG_POLISH with ``rescue`` (OSQP's polish=True for a breakdown at the rounding
     floor: the active set taken as exact, the equality-constrained QP solved; PlannerLPV's default);
-    ``stamps``: optional device address of a batch x 16 uint64 buffer (per-section clock counts).
+    ``stamps``: optional device address of a batch x 16 uint64 buffer (per-section clock counts);
+    ``duals``: also return the dual solution in OSQP's form (cmpc_solve_mpc_batch_duals, cmpc.duals): y
+    (B, m + (nx+ns)(N+1) + nu N), rows ordered [G; A], and dua_res (B,) = ||P z + q + [G; A]'y||_inf; an agent
+    whose exit holds no multipliers of the iterate it returns (never one with status 1) has NaN there.  The
+    fp32 and lane paths have none (CmpcError, CMPC_ERR_UNSUPPORTED).
 
-    Returns (z (B,nz), kkt (B,), iters (B,), status (B,))."""
+    Returns (z (B,nz), kkt (B,), iters (B,), status (B,)), with ``duals`` (z, kkt, iters, status, y, dua_res)."""
     ctx = ctx or L.default_context()
     batch = int(p["A"].shape[0])
     check_shapes(p, batch)
@@ -107,6 +111,16 @@ def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, g
     out = L.cmpc_mpc_out(L.dptr(z), L.dptr(kkt), L.iptr(iters), L.iptr(status))
     o = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, _flags(fp32, riccati, generic, rescue, lane, polish),
                stamps)
+    if duals:
+        from .duals import ny_of
+
+        y = np.zeros((batch, ny_of(p)))
+        dua = np.zeros(batch)
+        du = L.cmpc_mpc_duals(L.dptr(y), L.dptr(dua))
+        ctx.check(ctx.lib.cmpc_solve_mpc_batch_duals(ctx.h, ct.byref(_dims(p, batch)), ct.byref(w), ct.byref(data),
+                                                     ct.byref(out), ct.byref(du), ct.byref(o)))
+        del keep, arrs
+        return z, kkt, iters, status, y, dua
     ctx.check(ctx.lib.cmpc_solve_mpc_batch(ctx.h, ct.byref(_dims(p, batch)), ct.byref(w), ct.byref(data),
                                            ct.byref(out), ct.byref(o)))
     del keep, arrs
@@ -131,7 +145,9 @@ def solve_mpc_dev(shared, dev, out, ctx=None, tol=None, max_iter=None, stream=No
                   lane=False):
     """Device-resident batch solve.  ``shared``: dict with dims + shared weights (host);
     ``dev``: dict of CUDA float64 tensors (PER_AGENT keys); ``out``: dict with
-    'z' (float64) and optional 'kkt' (float64), 'iters', 'status' (int32) tensors.
+    'z' (float64) and optional 'kkt' (float64), 'iters', 'status' (int32) tensors; with a 'y' tensor
+    (float64, B x cmpc.duals.ny_of) and optionally 'dua_res' (float64, B) the dual solution is written too
+    (cmpc_solve_mpc_batch_duals_dev, one more launch on the same stream).
     Launches asynchronously on ``stream`` (default: torch's current stream)."""
     import torch
 
@@ -142,9 +158,15 @@ def solve_mpc_dev(shared, dev, out, ctx=None, tol=None, max_iter=None, stream=No
     o_ = L.cmpc_mpc_out(_tptr(out["z"]), _tptr(out.get("kkt")), _tptr(out.get("iters")), _tptr(out.get("status")))
     s = stream if stream is not None else torch.cuda.current_stream(dev["A"].device)
     o = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, _flags(fp32, riccati, lane=lane))
-    ctx.check(ctx.lib.cmpc_solve_mpc_batch_dev(ctx.h, ct.byref(_dims(shared, batch)), ct.byref(w),
-                                               ct.byref(data), ct.byref(o_), ct.byref(o),
-                                               ct.c_void_p(s.cuda_stream)))
+    if out.get("y") is not None:
+        du = L.cmpc_mpc_duals(_tptr(out["y"]), _tptr(out.get("dua_res")))
+        ctx.check(ctx.lib.cmpc_solve_mpc_batch_duals_dev(ctx.h, ct.byref(_dims(shared, batch)), ct.byref(w),
+                                                         ct.byref(data), ct.byref(o_), ct.byref(du), ct.byref(o),
+                                                         ct.c_void_p(s.cuda_stream)))
+    else:
+        ctx.check(ctx.lib.cmpc_solve_mpc_batch_dev(ctx.h, ct.byref(_dims(shared, batch)), ct.byref(w),
+                                                   ct.byref(data), ct.byref(o_), ct.byref(o),
+                                                   ct.c_void_p(s.cuda_stream)))
     del keep
 
 

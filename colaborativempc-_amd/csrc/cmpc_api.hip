@@ -210,16 +210,32 @@ int cmpc_comm_destroy(cmpc_ctx* ctx) {
 
 const char* cmpc_last_error(const cmpc_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-int cmpc_solve_mpc_batch_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
-                             const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_opts* opts,
-                             void* stream) {
-    if (!ctx) return CMPC_ERR_ARG;
-    if (!in || !out || !out->z) return fail(ctx, CMPC_ERR_ARG, "null data / output");
+// the multiplier area of the duals entry points (MpcConst::duals): fp64 solvers other than the lane kernel
+static int want_duals(cmpc_ctx* ctx, cmpc::MpcConst* c) {
+    if (c->lane || c->f32)
+        return fail(ctx, CMPC_ERR_UNSUPPORTED, "the fp32 and lane-per-agent paths return no dual solution");
+    c->duals = 1;
+    return CMPC_OK;
+}
+
+// the dual kernel behind a solve: lambda and its marker from the agents' multiplier areas
+static hipError_t duals_after(const cmpc::MpcConst& c, const cmpc::MpcPtrs& p, const cmpc_mpc_duals* du, int batch,
+                              hipStream_t s) {
+    const unsigned long long stride = cmpc::mpc_ws_doubles(c);
+    const double* area = p.ws + (stride - cmpc::duals_doubles(c));
+    return cmpc::mpc_dual_launch(c, p, p.z, area + 1, stride, area, stride, du->y, du->dua_res, batch, s);
+}
+
+// cmpc_solve_mpc_batch_dev, and with `du` cmpc_solve_mpc_batch_duals_dev
+static int solve_mpc_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                         const cmpc_mpc_out* out, const cmpc_mpc_duals* du, const cmpc_opts* opts, void* stream) {
     cmpc::MpcConst c;
     const char* msg = nullptr;
     int rc = cmpc::mpc_prepare(dims, w, opts, &c, &msg);
     if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (du && (rc = want_duals(ctx, &c)) != CMPC_OK) return rc;
     if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    if (du && dims->batch == 0) return CMPC_OK;
     double* ws = nullptr;
     int* plist = nullptr;
     if (const size_t wsd = cmpc::mpc_ws_doubles(c) * (size_t)dims->batch) {
@@ -233,6 +249,42 @@ int cmpc_solve_mpc_batch_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmp
     p.order = opts ? opts->order : nullptr;
     p.plist = plist;
     HIP_TRY(cmpc::mpc_launch(c, p, dims->batch, (hipStream_t)stream, opts ? opts->flags : 0));
+    if (du) HIP_TRY(duals_after(c, p, du, dims->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
+int cmpc_solve_mpc_batch_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                             const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_opts* opts,
+                             void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!in || !out || !out->z) return fail(ctx, CMPC_ERR_ARG, "null data / output");
+    return solve_mpc_dev(ctx, dims, w, in, out, nullptr, opts, stream);
+}
+
+int cmpc_solve_mpc_batch_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                                   const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_mpc_duals* duals,
+                                   const cmpc_opts* opts, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!dims || !in || !out || !out->z || !duals || !duals->y) return fail(ctx, CMPC_ERR_ARG, "null data / output");
+    return solve_mpc_dev(ctx, dims, w, in, out, duals, opts, stream);
+}
+
+int cmpc_mpc_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                       const double* z, const double* lam, const cmpc_mpc_duals* duals, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!dims || !in || !duals || !duals->y) return fail(ctx, CMPC_ERR_ARG, "null data / output");
+    cmpc::MpcConst c;
+    const char* msg = nullptr;
+    int rc = cmpc::mpc_prepare(dims, w, nullptr, &c, &msg);
+    if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (dims->batch == 0) return CMPC_OK;
+    if (!z || (c.m && !lam) || !in->A || !in->B || !in->qlin || (c.ms && (!in->C || !in->h)))
+        return fail(ctx, CMPC_ERR_ARG, "null data / output");
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    cmpc::MpcPtrs p{in->A, in->B, nullptr, nullptr, in->qlin, in->C, in->h, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr};
+    HIP_TRY(cmpc::mpc_dual_launch(c, p, z, lam, (unsigned long long)c.m, nullptr, 0, duals->y, duals->dua_res,
+                                  dims->batch, (hipStream_t)stream));
     return CMPC_OK;
 }
 
@@ -267,20 +319,23 @@ int cmpc_plan_mpc(const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cm
     return CMPC_OK;
 }
 
-int cmpc_solve_mpc_batch(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weights* w,
-                         const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_opts* opts) {
-    if (!ctx) return CMPC_ERR_ARG;
-    if (!d || !in || !out || !out->z) return fail(ctx, CMPC_ERR_ARG, "null argument");
+// cmpc_solve_mpc_batch, and with `dl` cmpc_solve_mpc_batch_duals
+static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                          const cmpc_mpc_out* out, const cmpc_mpc_duals* dl, const cmpc_opts* opts) {
     cmpc::MpcConst c;
     const char* msg = nullptr;
     int rc = cmpc::mpc_prepare(d, w, opts, &c, &msg);
     if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (dl && (rc = want_duals(ctx, &c)) != CMPC_OK) return rc;
     if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    if (dl && d->batch == 0) return CMPC_OK;
     const size_t B = d->batch, N = d->N, nx = d->nx, nu = d->nu, mc = d->mc;
     const size_t sA = B * N * nx * nx, sB = B * N * nx * nu, sx = B * nx, su = B * nu, sp = B * (N + 1) * nx,
                  sC = B * N * mc * nx, sh = B * N * mc, sz = B * mpc_nz(*d);
     const size_t sw = cmpc::mpc_ws_doubles(c) * B;
-    const size_t bytes = 8 * (sA + sB + sx + su + sp + sC + sh + sz + B + sw) + 8 * B + 4 * (B + 1) + 16 * 256;
+    const size_t sy = dl ? B * ((size_t)c.m + (size_t)(d->nx + d->ns) * (N + 1) + nu * N) : 0;
+    const size_t bytes = 8 * (sA + sB + sx + su + sp + sC + sh + sz + B + sw + sy + (dl ? B : 0)) + 8 * B +
+                         4 * (B + 1) + 16 * 256 + (dl ? 2 * 256 : 0);
     char* base = arena(ctx, bytes);
     if (!base) return fail(ctx, CMPC_ERR_NOMEM, "device arena allocation failed");
     Carve cv{base};
@@ -290,6 +345,7 @@ int cmpc_solve_mpc_batch(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_w
     int *di = cv.take<int>(B), *ds = cv.take<int>(B);
     double* dw = sw ? cv.take<double>(sw) : nullptr;
     int* dpl = sw ? cv.take<int>(B + 1) : nullptr;  // the polish launch's compacted agent list
+    double *dy = dl ? cv.take<double>(sy) : nullptr, *dr = dl ? cv.take<double>(B) : nullptr;
     hipStream_t s = ctx->stream;
     HIP_TRY(hipMemcpyAsync(dA, in->A, 8 * sA, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dB, in->B, 8 * sB, hipMemcpyHostToDevice, s));
@@ -302,12 +358,33 @@ int cmpc_solve_mpc_batch(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_w
                     opts ? (unsigned long long*)opts->stamps : nullptr, dw};  // stamps: device memory
     p.plist = dpl;
     HIP_TRY(cmpc::mpc_launch(c, p, d->batch, s, opts ? opts->flags : 0));
+    if (dl) {
+        const cmpc_mpc_duals dd{dy, dr};
+        HIP_TRY(duals_after(c, p, &dd, d->batch, s));
+        HIP_TRY(hipMemcpyAsync(dl->y, dy, 8 * sy, hipMemcpyDeviceToHost, s));
+        if (dl->dua_res) HIP_TRY(hipMemcpyAsync(dl->dua_res, dr, 8 * B, hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(hipMemcpyAsync(out->z, dz, 8 * sz, hipMemcpyDeviceToHost, s));
     if (out->kkt) HIP_TRY(hipMemcpyAsync(out->kkt, dk, 8 * B, hipMemcpyDeviceToHost, s));
     if (out->iters) HIP_TRY(hipMemcpyAsync(out->iters, di, 4 * B, hipMemcpyDeviceToHost, s));
     if (out->status) HIP_TRY(hipMemcpyAsync(out->status, ds, 4 * B, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return CMPC_OK;
+}
+
+int cmpc_solve_mpc_batch(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weights* w,
+                         const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_opts* opts) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!d || !in || !out || !out->z) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    return solve_mpc_host(ctx, d, w, in, out, nullptr, opts);
+}
+
+int cmpc_solve_mpc_batch_duals(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weights* w,
+                               const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_mpc_duals* duals,
+                               const cmpc_opts* opts) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!d || !in || !out || !out->z || !duals || !duals->y) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    return solve_mpc_host(ctx, d, w, in, out, duals, opts);
 }
 
 // Workspace layout of the LPV path (device): structured problem + error flags + solver scratch.

@@ -33,7 +33,10 @@ struct MpcConst {
     int f32;      // 1: CMPC_FLAG_FP32 on the stage-wise Riccati kernel (Cfg::F32; riccati = 1 as well)
     int polish;   // 1: CMPC_FLAG_POLISH (with rescue): active-set polish of breakdowns at the rounding floor
     int waves;    // fused DS instantiation of the v3 kernel: wavefronts per agent (0, 1: one; 2: CMPC_FLAG_TWO_WAVES)
+    int duals;    // 1: the cmpc_solve_mpc_batch_duals entry points (no public flag): every exit that writes an agent's
+                  // z leaves that iterate's inequality multipliers in the agent's scratch (duals_doubles below)
     unsigned long long ws_stride;  // doubles of MpcPtrs::ws per agent (set by mpc_launch; 0: no scratch)
+    unsigned long long duals_off;  // the multiplier area's offset in the agent's scratch (set by mpc_launch)
     double tol;
     double qs_max;  // max(1, 2*max(Qs)) — slack residual scale
     double R[CMPC_MAX_NU * CMPC_MAX_NU];
@@ -161,6 +164,14 @@ __host__ __device__ inline size_t hand_doubles(const MpcConst& c) {
     return 2 + (size_t)c.n + (size_t)c.N * c.ns + 2 * (size_t)c.m;
 }
 __host__ __device__ inline size_t hand_t(const MpcConst& c) { return 2 + (size_t)c.n + (size_t)c.N * c.ns; }
+// Multiplier area (MpcConst::duals), after everything else in the agent's scratch (the rescue image stays first):
+//   [marker, lambda (m)]   (rows in the oracle's order)
+// marker 1.0: lambda belongs to the z the agent returned (a converged exit, or a polish that replaced the endpoint);
+// 0.0: the exit restored a best iterate whose multipliers it does not hold (stall, iteration cap, breakdown).  A
+// later launch on the same agent (the Riccati continuation, the polish) overwrites both with what it returns.
+__host__ __device__ inline size_t duals_doubles(const MpcConst& c) {
+    return c.duals ? ((1 + (size_t)c.m + 31) & ~size_t(31)) : 0;
+}
 // A continued (handed-over) solve without a new best iterate for kWarmStall iterations ends there
 // (best iterate; CMPC_UNSOLVED above the rounding floor, which the cold second pass re-solves).
 // Over 22 closed-loop rounds of bench.py's lpv_rounds population (tools/lpv_lab.py, the C
@@ -197,7 +208,8 @@ hipError_t mpc_lane_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipSt
 // Device scratch (doubles per agent) the solver chosen for c needs in MpcPtrs::ws (0: none).
 inline size_t mpc_ws_doubles(const MpcConst& c) {
     if (c.lane) return mpc_lane_ws_doubles(c);
-    return (c.riccati || c.rescue) ? mpc_riccati_ws_doubles(c) : 0;
+    // (mpc_riccati_ws_doubles counts the multiplier area of MpcConst::duals itself, as its last region)
+    return (c.riccati || c.rescue) ? mpc_riccati_ws_doubles(c) : duals_doubles(c);
 }
 
 // Fills the derived fields of MpcConst; returns CMPC_OK or an error code with msg.
@@ -211,6 +223,12 @@ bool mpc3_try_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t
 // LDS bytes of the v3 instantiation mpc3_try_launch would run for c (0: none covers it)
 size_t mpc3_lds_bytes(const MpcConst& c);
 size_t mpc_lane_lds_bytes(const MpcConst& c);
+// Dual solution in OSQP's form (mpc_dual.hip): y (batch x (m + ne (N + 1) + nu N)) and dua_res (batch, may be
+// null) from z and agent b's multipliers at lam + b * lam_stride; valid (may be null): agent b's marker at
+// valid + b * valid_stride, anything but 1.0 gives NaN outputs.  Reads A, B, p, C, h of `p` only
+hipError_t mpc_dual_launch(const MpcConst& c, const MpcPtrs& p, const double* z, const double* lam,
+                           unsigned long long lam_stride, const double* valid, unsigned long long valid_stride,
+                           double* y, double* dua_res, int batch, hipStream_t s);
 
 // LPV reference-semantics builder (scheduling + planes + weights + rows).
 struct LpvConst {

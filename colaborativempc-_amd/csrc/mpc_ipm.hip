@@ -655,6 +655,12 @@ __global__ __launch_bounds__(kWave) void mpc_ipm_kernel(const MpcConst c, const 
             hd[ht + m + r] = lam[r];
         }
     }
+    if (c.duals && P.ws) {  // the returned iterate's multipliers (duals_doubles, internal.h): a converged exit's only
+        double* da = P.ws + (size_t)b * c.ws_stride + c.duals_off;
+        if (stop == kStopConverged)
+            for (int r = l; r < m; r += kWave) da[1 + r] = lam[r];
+        if (l == 0) da[0] = stop == kStopConverged ? 1.0 : 0.0;
+    }
     if (stop != kStopConverged) {
         if (best_it > 0) {  // restore the best iterate
             for (int i = l; i < n; i += kWave) U[i] = bU[i];
@@ -817,6 +823,8 @@ hipError_t mpc_launch(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStre
     if (batch == 0) return hipSuccess;
     MpcConst c = c_in;
     c.ws_stride = p.ws ? mpc_ws_doubles(c) : 0;
+    if (c.duals && (!p.ws || c.lane || c.f32)) return hipErrorInvalidValue;
+    c.duals_off = c.duals ? c.ws_stride - duals_doubles(c) : 0;
     if (c.lane) return mpc_lane_launch(c, p, batch, s);
     if (c.riccati) {
         hipError_t er = mpc_riccati_launch(c, p, batch, s);

@@ -1842,6 +1842,19 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
           (best_m < 1e3 * c.tol || stop == kStopMaxIter)) ||
          degen))
         write_image();
+    // the returned iterate's multipliers (duals_doubles, internal.h): a converged exit's only.  Not in the DS
+    // instantiations: they run the fused double-integrator round alone, which keeps none
+    if constexpr (!DS) {
+        if (c.duals && P.ws) {
+            double* da = P.ws + (size_t)b * c.ws_stride + c.duals_off;
+            if (stop == kStopConverged && own) {
+#pragma unroll
+                for (int r = 0; r < RX; ++r)
+                    if (lo ? r < MC : r < NI) da[1 + (lo ? 0 : ms) + k * (lo ? MC : NI) + r] = lam[r];
+            }
+            if (l == 0) da[0] = stop == kStopConverged ? 1.0 : 0.0;
+        }
+    }
     if (stop != kStopConverged) {
         if (best_it > 0) {  // restore the best iterate
             for (int i = l; i < NP; i += 64) U[i] = bU[i];

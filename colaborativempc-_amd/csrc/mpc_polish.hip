@@ -1262,6 +1262,14 @@ __global__ __launch_bounds__(kPT) void mpc_polish_kernel(const MpcConst c_arg, c
         }
         PSTAMP(5);
         if (mp < best) {
+            // the multipliers of the point kept, max(lambda_A, 0) on A and 0 elsewhere (lamp as the evaluation above
+            // left it), into the multiplier area (duals_doubles, internal.h) — only from a pass whose point the
+            // test after the passes accepts: the last such pass is then the one whose point is returned, and an
+            // agent whose endpoint stays keeps the solver's area
+            if (c.duals && mp < best_m && mp < 1e3 * c.tol) {
+                double* da = hd + c.duals_off;
+                for (int r = tid; r < m; r += kPT) da[1 + r] = lamp[r];
+            }
             best = mp;
             best_kkt = kk;
             for (int i = tid; i < n; i += kPT) Ub[i] = Uc[i];
@@ -1331,6 +1339,7 @@ __global__ __launch_bounds__(kPT) void mpc_polish_kernel(const MpcConst c_arg, c
         if (P.kkt) P.kkt[b] = best_kkt;
         if (P.status) P.status[b] = best < c.tol ? CMPC_SOLVED : CMPC_SOLVED_INACCURATE;
         hd[0] = 0.0;
+        if (c.duals) hd[c.duals_off] = 1.0;  // (the area holds this point's multipliers, written above)
     }
 }
 

@@ -235,7 +235,7 @@ __host__ __device__ inline RLds r_layout(const MpcConst& c) { return r_layout_ex
 // per-agent global scratch (doubles): predictor direction (dt, dl), Riccati factors, stage
 // weights W_k = 2Q + M_k of the state X_{k+1}, best iterate
 struct RGlb {
-    size_t hand, dta, dla, F, Wk, bU, bsig, t, lam, w, rp, rho, GdU, total;
+    size_t hand, dta, dla, F, Wk, bU, bsig, t, lam, w, rp, rho, GdU, dual, total;
 };
 
 __host__ __device__ inline RGlb r_glb(const MpcConst& c) {
@@ -261,6 +261,7 @@ __host__ __device__ inline RGlb r_glb(const MpcConst& c) {
     g.rp = take(mr);
     g.rho = take(mr);
     g.GdU = take(mr);
+    g.dual = take(duals_doubles(c));  // last (MpcConst::duals_off = total - duals_doubles)
     g.total = o;
     return g;
 }
@@ -2474,6 +2475,12 @@ __global__ __launch_bounds__(kWave) void mpc_riccati_kernel(const MpcConst c_arg
         z[(size_t)(N + 1) * nxe + i] = U[i];
         z[(size_t)(N + 1) * nxe + n + i] = U[i] - (k ? U[(k - 1) * nu + j] : up[j]);
     }
+    if (c.duals) {  // the returned iterate's multipliers (duals_doubles, internal.h): held by a converged exit only
+        double* da = ws + gl.dual;
+        if (stop == kStopConverged)
+            for (int r = l; r < m; r += kWave) da[1 + r] = lam[r];
+        if (l == 0) da[0] = stop == kStopConverged ? 1.0 : 0.0;
+    }
     if (l == 0) {
         if (P.kkt) P.kkt[b] = kkt;
         if (P.iters) P.iters[b] = it_prev + it_done + it;
@@ -3051,6 +3058,12 @@ __global__ __launch_bounds__(kMW * kWave) void mpc_riccati_mw_kernel(const MpcCo
         const int k = i / nu, j = i - k * nu;
         z[(size_t)(N + 1) * nxe + i] = U[i];
         z[(size_t)(N + 1) * nxe + n + i] = U[i] - (k ? U[(k - 1) * nu + j] : up[j]);
+    }
+    if (c.duals) {  // the returned iterate's multipliers (duals_doubles, internal.h): held by a converged exit only
+        double* da = ws + gl.dual;
+        if (stop == kStopConverged)
+            for (int r = tid; r < m; r += NT) da[1 + r] = lam[r];
+        if (tid == 0) da[0] = stop == kStopConverged ? 1.0 : 0.0;
     }
     if (tid == 0) {
         if (P.kkt) P.kkt[b] = kkt;

@@ -48,7 +48,8 @@ extern "C" {
                                 still 6 (additions only: no struct grew, no entry point changed):
                                 cmpc_nbr_select_dev, CMPC_ROUNDS_RESELECT; cmpc_order_by_iters_dev,
                                 cmpc_di_rounds_*, CMPC_ROUNDS_LPT; cmpc_round_log_dev,
-                                cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, CMPC_LOG_SEPARATION */
+                                cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, CMPC_LOG_SEPARATION;
+                                cmpc_mpc_duals, cmpc_solve_mpc_batch_duals[_dev], cmpc_mpc_duals_dev */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -194,6 +195,47 @@ int cmpc_solve_mpc_batch(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mp
 int cmpc_solve_mpc_batch_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                              const cmpc_mpc_data* dev_in, const cmpc_mpc_out* dev_out,
                              const cmpc_opts* opts, void* hip_stream);
+
+/* The dual solution of the same QP in OSQP's form (the reference's res.y).  With the inequalities G z <= h in
+ * the order above (the stage rows k = 1..N, r < mc, then per stage and input [u_i <= ub_i; -u_i <= -lb_i]:
+ * m = N mc + 2 nu N rows) and the equalities A z = b ((nx+ns)(N+1) rows: x_0 = x0, the dynamics, an empty
+ * 0 = 0 row per slack; then nu N input-rate rows), OSQP stacks [G; A]:
+ *
+ *   y = [y_G (m) | y_A ((nx+ns)(N+1) + nu N)],   stationarity  P z + q + G'y_G + A'y_A = 0.
+ *
+ * y_G is the interior-point multiplier lambda >= 0 of the iterate returned in z; a row whose bound is infinite
+ * has y exactly 0.  y_A follows from z and y_G:
+ *   input-rate rows   nu_d,0 = 2 dR du_0,  nu_d,i = -2 dR du_i  (i >= 1)
+ *   state rows        g_k = 2 Q x_k + 2 qlin_k + C_k' lambda_k  (the last term for k >= 1)
+ *                     nu_N = -g_N,  nu_k = A_k' nu_{k+1} - g_k  (k = N-1 .. 0)     (the costates)
+ *   slack rows        exactly 0
+ * so the x and du columns of the stationarity vector vanish by construction and the u and slack columns carry
+ * the dual residual; dua_res = ||P z + q + [G; A]'y||_inf, unscaled (OSQP's info.dua_res).
+ *
+ * An agent whose exit does not hold the multipliers of the iterate it returns (a stall, iteration-cap or
+ * breakdown exit short of tolerance restores its best iterate) and an agent whose z is not finite get an
+ * all-NaN y row and a NaN dua_res.  A solve that ends at CMPC_SOLVED always has its dual solution; so does
+ * every point the polish (CMPC_FLAG_POLISH) returns: max(lambda_A, 0) on its active set, 0 elsewhere.
+ * z, kkt, iters and status are bit-identical to cmpc_solve_mpc_batch[_dev] with the same options.
+ * CMPC_FLAG_FP32 and CMPC_FLAG_LANE: CMPC_ERR_UNSUPPORTED.  A NULL duals or duals->y: CMPC_ERR_ARG; batch == 0:
+ * CMPC_OK without a launch. */
+typedef struct {
+    double* y;        /* batch x (m + (nx+ns)(N+1) + nu N), OSQP order [G rows; A rows] */
+    double* dua_res;  /* batch (may be NULL) */
+} cmpc_mpc_duals;
+
+int cmpc_solve_mpc_batch_duals(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                               const cmpc_mpc_data* host_in, const cmpc_mpc_out* host_out,
+                               const cmpc_mpc_duals* host_duals, const cmpc_opts* opts);
+int cmpc_solve_mpc_batch_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                                   const cmpc_mpc_data* dev_in, const cmpc_mpc_out* dev_out,
+                                   const cmpc_mpc_duals* dev_duals, const cmpc_opts* opts, void* hip_stream);
+/* The dual kernel alone (one launch, graph-capturable): z = batch x nz and lam = batch x m inequality
+ * multipliers in G's row order, both on the device; of dev_in it reads A, B, qlin, C and h.  An agent with a
+ * non-finite z gets the NaN row; a NaN in lam at a finite-bound row propagates into that agent's outputs. */
+int cmpc_mpc_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                       const cmpc_mpc_data* dev_in, const double* z, const double* lam,
+                       const cmpc_mpc_duals* dev_duals, void* hip_stream);
 
 /* The solver a structured batch would run, and how many of its workgroups share a CU — host only
  * (no context, no device).  Every solver uses more than 256 VGPRs + AGPRs per lane, so one

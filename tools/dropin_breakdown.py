@@ -52,8 +52,8 @@ def main(reps):
             z, kkt, it, st = solve_mpc(St.stack([p]), ctx, rescue=True, polish=True)
             t2 = time.perf_counter()
             x = z[0]
-            Q._osqp_result(x, int(st[0]), "solved", int(it[0]), float(0.5 * x @ (P @ x) + q @ x), float(kkt[0]),
-                           Q._pri_res(x, G, h, A, b), "structured")
+            Q._osqp_result(x, None, int(st[0]), "solved", int(it[0]), float(0.5 * x @ (P @ x) + q @ x), float(kkt[0]),
+                           Q._pri_res(x, G, h, A, b), float("nan"), "structured")
             t3 = time.perf_counter()
             cmpc.osqp_solve_qp(P, q, G, h, A, b, ctx=ctx)
             t4 = time.perf_counter()
