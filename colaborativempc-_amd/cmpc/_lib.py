@@ -46,6 +46,7 @@ CMPC_FLAG_LANE = 128    # lane-per-agent stage-wise kernel, fp64
 CMPC_FLAG_POLISH = 256  # with RESCUE: active-set polish of breakdowns at the rounding floor (OSQP polish=True)
 CMPC_FLAG_ONE_WAVE = 512   # fused DS round: one wavefront per agent (the default)
 CMPC_FLAG_TWO_WAVES = 1024  # ... two wavefronts per agent (opt-in: bit-identical, no faster at 512 agents)
+CMPC_FLAG_LTI = 2048   # the caller's promise: A_k, B_k bit-equal to stage 0's at every stage, all finite (rounds.is_lti)
 
 
 class cmpc_opts(ct.Structure):

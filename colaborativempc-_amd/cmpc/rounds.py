@@ -185,6 +185,21 @@ def _lpt_default(sh, N, fp32):
     return N * sh["nu"] > 64 and (not fp32 or ric32)
 
 
+def is_lti(A, B):
+    """Whether the agents' models are time-invariant in the sense of CMPC_FLAG_LTI: ``A`` (batch, N, nx, nx) and
+    ``B`` (batch, N, nx, nu) are fp64, every stage of an agent is bit-equal to its stage 0 (compared as 64-bit
+    patterns: -0.0 is not +0.0) and every entry is finite.  The test ``cmpc_di_rounds_create`` runs on its
+    host arrays."""
+    for M in (A, B):
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if M.ndim != 4 or not np.isfinite(M).all():
+            return False
+        bits = M.view(np.uint64)
+        if not (bits == bits[:, :1]).all():
+            return False
+    return True
+
+
 class _TorchRounds:
     """What the torch-driven ``DIRounds`` / ``LPVRounds`` share; they set ``torch``, ``dev``, ``ctx``, the shard
     (``B``, ``off``, ``nb``, ``world``, ``group``, ``comm``), ``traj_all`` / ``traj_local`` / ``nbr`` and
@@ -286,10 +301,14 @@ class DIRounds(_TorchRounds):
     round's stream, before the rows are built), so the collision rows and the coverage term follow the agents
     that are nearest now instead of those of the scenario's t = 0 table.  0 (the default): the table stays
     what the scenario gave, and ``step()`` is launch for launch what it was.  Selected neighbours come nearest
-    first, not in the reference's index order of ns[i]; only the order of an agent's collision rows follows."""
+    first, not in the reference's index order of ns[i]; only the order of an agent's collision rows follows.
+
+    ``lti``: CMPC_FLAG_LTI, the promise that every stage of an agent's A and B equals its stage 0 (the fused
+    round then tabulates the condensed dynamics once per solve, same bits).  None (the default): set when
+    ``is_lti`` finds it so on this rank's ``scen.A``, ``scen.B``; False: never; True: set without the test."""
 
     def __init__(self, scen, rank=0, world=1, device=None, ctx=None, tol=None, max_iter=None, group=None,
-                 fp32=False, comm=None, fused=True, lpt=None, reselect=0, reselect_window=(0, 0)):
+                 fp32=False, comm=None, fused=True, lpt=None, reselect=0, reselect_window=(0, 0), lti=None):
         import torch
 
         self.torch = torch
@@ -330,6 +349,10 @@ class DIRounds(_TorchRounds):
         self.mdims = _dims(sh, self.B)
         self.w, self._wkeep = _weights(sh)
         self.opts = _di_opts(tol, max_iter, fp32)
+        # CMPC_FLAG_LTI: set when this rank's A, B pass is_lti (None), never (False) or untested (True)
+        self.lti = is_lti(scen.A[sl], scen.B[sl]) if lti is None else bool(lti)
+        if self.lti:
+            self.opts.flags |= L.CMPC_FLAG_LTI
         self.lpt = _lpt_default(sh, self.N, fp32) if lpt is None else bool(lpt)   # cmpc_opts.order
         self._order = None
         self.data = L.cmpc_mpc_data(*[_tptr(t) for t in (self.A, self.Bm, self.x0, self.u_prev, self.qlin,

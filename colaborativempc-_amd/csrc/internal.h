@@ -33,6 +33,8 @@ struct MpcConst {
     int f32;      // 1: CMPC_FLAG_FP32 on the stage-wise Riccati kernel (Cfg::F32; riccati = 1 as well)
     int polish;   // 1: CMPC_FLAG_POLISH (with rescue): active-set polish of breakdowns at the rounding floor
     int waves;    // fused DS instantiation of the v3 kernel: wavefronts per agent (0, 1: one; 2: CMPC_FLAG_TWO_WAVES)
+    int lti;      // 1: CMPC_FLAG_LTI (A_k = A_0, B_k = B_0, finite): the fused DS instantiation's one-wave mode reads
+                  // stage 0 only and tabulates the condensed dynamics once per solve (mpc_ipm3.hip, TI)
     int duals;    // 1: the cmpc_solve_mpc_batch_duals entry points (no public flag): every exit that writes an agent's
                   // z leaves that iterate's inequality multipliers in the agent's scratch (duals_doubles below)
     unsigned long long ws_stride;  // doubles of MpcPtrs::ws per agent (set by mpc_launch; 0: no scratch)

@@ -788,6 +788,7 @@ int mpc_prepare(const cmpc_mpc_dims* d, const cmpc_mpc_weights* wt, const cmpc_o
         return CMPC_ERR_ARG;
     }
     c->waves = (o && (o->flags & CMPC_FLAG_TWO_WAVES)) ? 2 : ((o && (o->flags & CMPC_FLAG_ONE_WAVE)) ? 1 : 0);
+    c->lti = (o && (o->flags & CMPC_FLAG_LTI)) ? 1 : 0;
     c->polish = 0;
     // (mpc_polish.hip: one lane per condensed variable in its H build, so n <= 64 — every condensed
     // solve, which is what carries the rescue image)

@@ -114,7 +114,7 @@ __host__ __device__ constexpr bool seg_on() {
     return !LS && NX <= 4 && NU <= 2 && T >= 2;
 }
 
-template <int T, int NX, int NU, int NB, bool LS = false, bool DS = false, bool W2 = false>
+template <int T, int NX, int NU, int NB, bool LS = false, bool DS = false, bool W2 = false, bool TI = false>
 __host__ __device__ inline Lds3 lds3_layout(int N) {
     constexpr int NP = 16 * T, MC = 4 + NB;
     Lds3 L{};
@@ -126,7 +126,9 @@ __host__ __device__ inline Lds3 lds3_layout(int N) {
     };
     L.cst = take(NX * NX + 2 * NU * NU + 3 + 2 * NU);
     L.A = take(LS ? N * NX * 3 : N * NX * NX);
-    L.B = take(LS ? N * 3 * NU : N * NX * NU);
+    // TI: the table of the condensed dynamics' columns (ti_slot) instead of the stages' B_k: the same size,
+    // and one all-zero slot
+    L.B = take(LS ? N * 3 * NU : (TI ? N + 1 : N) * NX * NU);
     L.C = take(LS ? N * ls_cw<NB>() : (DS ? N * ds_cw<NB>() : N * MC * NX));
     L.H = take(N * MC);
     L.Pq = take((N + 1) * NX);
@@ -175,12 +177,24 @@ __host__ __device__ inline Lds3 lds3_layout(int N) {
     return L;
 }
 
+// TI (time-invariant agents, CMPC_FLAG_LTI: A_k = A, B_k = B at every stage): column kc NU + ic of the
+// condensed dynamics Gamma_{k+1} is A^(k - kc) B[:, ic] for k >= kc and zero before, so the columns of every
+// stage are the table G[d][ic][:] = A^d B[:, ic], d = 0 .. N-1, as large as the image of the stages' B_k
+// whose place it takes; G[0] = B.  Slot N is all zero (d < 0).  A lane's NX values are contiguous.
+template <int NX, int NU>
+__host__ __device__ constexpr int ti_slot(int d, int ic) { return (d * NU + ic) * NX; }
+// index of B_k[r][j] in the B image: the stage's own entry, or (TI) the table's slot 0
+template <int NX, int NU, bool TI>
+__host__ __device__ constexpr int ti_b(int k, int r, int j) {
+    return TI ? ti_slot<NX, NU>(0, j) + r : (k * NX + r) * NU + j;
+}
+
 // x_0 = x0 (LDS, or 0), x_{k+1} = A_k x_k + B_k u_k.  Lane (l & 15) = s < NX of every row of
 // 16 carries x_s (the rows are duplicates; lanes with s >= NX duplicate x_0); x_t reaches the
 // row by DPP row_newbcast.  A stage's A row and B u term are fetched two stages ahead into
 // rotating register sets (unrolled by three: no copies, no branches; the fetch index is clamped
 // instead of guarded).  Every lane stores: duplicates write equal values.
-template <int NX, int NU, bool LS = false>
+template <int NX, int NU, bool LS = false, bool TI = false>
 __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double* B, const double* x0,
                                      const double* U, double* X) {
     static_assert(NX <= 16, "row broadcast");
@@ -201,7 +215,7 @@ __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double
             v = r < 3 ? v : 0.0;
         } else {
 #pragma unroll
-            for (int j = 0; j < NU; ++j) v = fma(B[(k * NX + r) * NU + j], U[k * NU + j], v);
+            for (int j = 0; j < NU; ++j) v = fma(B[ti_b<NX, NU, TI>(k, r, j)], U[k * NU + j], v);
         }
         X[NX + i] = v;
     }
@@ -289,7 +303,7 @@ __device__ __forceinline__ double phi_apply(const double* phr, const double* xa,
 }
 
 // fwd3 (x_0 = x0 or 0, x_{k+1} = A_k x_k + B_k u_k) by segments (seg_a, phi_build); X, U, A, B as fwd3.
-template <int NX, int NU>
+template <int NX, int NU, bool TI = false>
 __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const double* B, const double* x0,
                                         const double* U, double* X, const double* Phi) {
     static_assert(NX <= 16, "row broadcast");
@@ -305,7 +319,7 @@ __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const dou
         for (int t = 0; t < NX; ++t) av[t] = A[(k * NX + s) * NX + t];
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
-            av[NX + j] = B[(k * NX + s) * NU + j];
+            av[NX + j] = B[ti_b<NX, NU, TI>(k, s, j)];
             av[NX + NU + j] = U[k * NU + j];
         }
     };
@@ -541,13 +555,13 @@ __device__ __forceinline__ void psi3(int l, int N, const double* A, double* y0, 
 }
 
 // o = B_k[:, i]' psi_{k+1} (psi as left in place by psi3): even/odd partial sums, as before
-template <int NX, int NU, bool LS = false>
+template <int NX, int NU, bool LS = false, bool TI = false>
 __device__ __forceinline__ double bpsi3(const double* B, const double* psi, int k, int i) {
     constexpr int NB_ = LS ? 3 : NX;  // LS: B_k is nonzero only in rows 0..2
     double v0 = 0.0, v1 = 0.0;
 #pragma unroll
     for (int t = 0; t < NB_; ++t) {
-        const double bt = B[(k * NB_ + t) * NU + i], pt = psi[(k + 1) * NX + t];
+        const double bt = B[TI ? ti_b<NX, NU, true>(k, t, i) : (k * NB_ + t) * NU + i], pt = psi[(k + 1) * NX + t];
         if (t & 1) v1 = fma(bt, pt, v1);
         else v0 = fma(bt, pt, v0);
     }
@@ -569,7 +583,12 @@ __device__ __forceinline__ double bpsi3(const double* B, const double* psi, int 
 //     (rho, C' rho~, the adjoint recursion, vb) and hands rho and vb over;
 //   * the triangular solves run on wave 0 only; wave 1 takes each pass's dU from LDS.
 // Wave 0 alone writes the outputs.
-template <int T, int NX, int NU, int NB, bool LS = false, bool DS = false, bool L5 = false, bool W2 = false>
+// TI (with DS, one wave): the agents are time-invariant (MpcConst::lti, the caller's promise CMPC_FLAG_LTI).  Stage 0
+// of A and B is read, the A image holds N copies of it, and the K build reads its Gamma columns from a table built
+// once per solve (ti_slot) instead of carrying them through A_k Gamma_k in every iteration: the same fmas on the
+// same operands in the same order, so the same bits.
+template <int T, int NX, int NU, int NB, bool LS = false, bool DS = false, bool L5 = false, bool W2 = false,
+          bool TI = false>
 __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcConst c, const MpcPtrs P) {
     constexpr int MC = 4 + NB, NS = 3, NT = T * (T + 1) / 2, NP = 16 * T, NXP = (NX + 3) & ~3;
     constexpr int NI = 2 * NU, RX = MC > NI ? MC : NI;
@@ -580,11 +599,12 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
     constexpr int CWD = ds_cw<NB>();  // DS: plane coefficients per stage
     extern __shared__ __attribute__((aligned(16))) double sm[];
     static_assert(!W2 || DS, "W2: the fused double-integrator instantiation");
+    static_assert(!TI || (DS && !W2), "TI: the one-wave fused double-integrator instantiation");
     const int l0 = threadIdx.x & 63, b = blockIdx.x, N = c.N, n = N * NU, ms = N * MC;
     const int l = l0;
     // the wave index as a scalar (wave-uniform: the branches on it are scalar, never exec-masked)
     const int wvi = W2 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    const Lds3 L = lds3_layout<T, NX, NU, NB, LS, DS, W2>(N);
+    const Lds3 L = lds3_layout<T, NX, NU, NB, LS, DS, W2, TI>(N);
     const int po = wvi * L.psz;  // this wave's private images
     double* Q2 = sm + L.cst;          // 2Q
     double* R2 = Q2 + NX * NX;        // 2R
@@ -644,6 +664,13 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 const int kk = i / CW, q = i - kk * CW;
                 const int r = q < 4 ? q : 4 + ((q - 4) >> 1), col = q < 2 ? 0 : (q < 4 ? 3 : 7 + ((q - 4) & 1));
                 sC[i] = gC[(kk * MC + r) * NX + col];
+            }
+        } else if constexpr (TI) {
+            // stage 0 only: N copies of A (the recursions index it by stage), B into the table's slot 0
+            for (int i = l; i < N * NX * NX; i += 64) sA[i] = gA[i % (NX * NX)];
+            for (int i = l; i < NX * NU; i += 64) {
+                sB[ti_b<NX, NU, true>(0, i / NU, i % NU)] = gB[i];
+                sB[ti_slot<NX, NU>(N, 0) + i] = 0.0;
             }
         } else {
             for (int i = l; i < N * NX * NX; i += 64) sA[i] = gA[i];
@@ -740,14 +767,41 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             if ((lo ? r < MC : r < NI) && isfinite(wv(r))) actm |= 1u << r;
     }
 #define ACT(r) ((actm >> (r)) & 1u)
+    if constexpr (TI) {
+        // the table: G[d + 1] = A G[d] from G[0] = B by the K build's own chain (v = 0; v = fma(A[s][u], g[u], v)),
+        // once per solve; lane ic < NU carries column ic
+        const int ic = l < NU ? l : 0;
+        double ar[NX * NX], g[NX];
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) ar[i] = sA[i];
+#pragma unroll
+        for (int s = 0; s < NX; ++s) g[s] = sB[ti_slot<NX, NU>(0, ic) + s];
+        for (int d = 1; d < N; ++d) {
+            double gn[NX];
+#pragma unroll
+            for (int s = 0; s < NX; ++s) {
+                double v = 0.0;
+#pragma unroll
+                for (int u = 0; u < NX; ++u) v = fma(ar[s * NX + u], g[u], v);
+                gn[s] = v;
+            }
+#pragma unroll
+            for (int s = 0; s < NX; ++s) g[s] = gn[s];
+            if (l < NU) {
+#pragma unroll
+                for (int s = 0; s < NX; ++s) sB[ti_slot<NX, NU>(d, ic) + s] = g[s];
+            }
+        }
+        wsync();
+    }
     constexpr bool kSeg = seg_on<T, NX, NU, LS>();
     double* sPhi = sm + L.Phi;
     // x_{k+1} = A_k x_k + B_k u_k, by segments where the instantiation has them.  The lane index is
     // an argument: inside the iteration loop it is the loop's own (opaque) copy, so the segment
     // bounds derived from it are recomputed there instead of hoisted and held across the loop
     auto fwd = [&](int lv, const double* x0v, const double* Uv, double* Xv) __attribute__((always_inline)) {
-        if constexpr (kSeg) fwd3seg<NX, NU>(lv, N, sA, sB, x0v, Uv, Xv, sPhi);
-        else fwd3<NX, NU, LS>(lv, N, sA, sB, x0v, Uv, Xv);
+        if constexpr (kSeg) fwd3seg<NX, NU, TI>(lv, N, sA, sB, x0v, Uv, Xv, sPhi);
+        else fwd3<NX, NU, LS, TI>(lv, N, sA, sB, x0v, Uv, Xv);
     };
     double* sPst = sm + L.Pst;
     if constexpr (kSeg) {
@@ -912,8 +966,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                         const double dun = (k + 1 < N) ? U[(k + 1) * NU + j] - uk : 0.0;
                         v += R2[i * NU + j] * uk + dR2[i * NU + j] * (duk - dun);
                     }
-                    const double g = bpsi3<NX, NU, LS>(sB, yb, k, i) + v;
-                    const double rdv = bpsi3<NX, NU, LS>(sB, dX, k, i) + v + lam[2 * i] - lam[2 * i + 1];
+                    const double g = bpsi3<NX, NU, LS, TI>(sB, yb, k, i) + v;
+                    const double rdv = bpsi3<NX, NU, LS, TI>(sB, dX, k, i) + v + lam[2 * i] - lam[2 * i + 1];
                     rd[ci] = rdv;
                     gs_l = nmax(gs_l, fabs(g));
                     nrd_l = nmax(nrd_l, fabs(rdv));
@@ -1235,8 +1289,10 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             //    loads that column once and selects it at its stage (A_k Gamma_k is exactly 0 there);
             //  * for small NX, A_k is fetched one stage ahead into ping-pong registers (the stage
             //    loop is unrolled by two: no copies); larger NX read A_k in place.
+            //  * TI: the column of stage k is the table's slot k - kc (the zero slot before kc, the clamp on the
+            //    address): no recursion; the ping-pong registers hold the next stage's column instead of A.
             constexpr bool kPf = NX * NX <= 16;
-            constexpr int PA = kPf ? NX * NX : 1;
+            constexpr int PA = TI ? NX : (kPf ? NX * NX : 1);
             double g[NX];
 #pragma unroll
             for (int s = 0; s < NX; ++s) g[s] = 0.0;
@@ -1244,10 +1300,15 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             const int kc = col / NU, ic = col - kc * NU, kcl = kc < N ? kc : N - 1;
             double bcol[NX];
 #pragma unroll
-            for (int s = 0; s < NX; ++s) bcol[s] = sB[(kcl * NX + s) * NU + ic];
+            for (int s = 0; s < NX; ++s) bcol[s] = TI ? 0.0 : sB[(kcl * NX + s) * NU + ic];
             double a0[PA], a1[PA];
             auto fetchA = [&](int kk, double* av) __attribute__((always_inline)) {
-                if constexpr (kPf) {
+                if constexpr (TI) {
+                    const unsigned d = (unsigned)(kk - kc);  // k < kc (and every padding lane, kc >= N): slot N
+                    const double* gp = sB + ti_slot<NX, NU>((int)(d < (unsigned)N ? d : (unsigned)N), ic);
+#pragma unroll
+                    for (int s = 0; s < NX; ++s) av[s] = gp[s];
+                } else if constexpr (kPf) {
 #pragma unroll
                     for (int i = 0; i < PA; ++i) av[i] = sA[kk * NX * NX + i];
                 }
@@ -1278,17 +1339,22 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     if constexpr (kPf) return wk[i];
                     else return Wk[i];
                 };
-                const bool inj = kk == kc;
-                double gn[NX];
+                if constexpr (TI) {
 #pragma unroll
-                for (int s = 0; s < NX; ++s) {
-                    double v = 0.0;
+                    for (int s = 0; s < NX; ++s) g[s] = av[s];
+                } else {
+                    const bool inj = kk == kc;
+                    double gn[NX];
 #pragma unroll
-                    for (int u = 0; u < NX; ++u) v = fma(A_(s * NX + u), g[u], v);
-                    gn[s] = inj ? bcol[s] : v;
+                    for (int s = 0; s < NX; ++s) {
+                        double v = 0.0;
+#pragma unroll
+                        for (int u = 0; u < NX; ++u) v = fma(A_(s * NX + u), g[u], v);
+                        gn[s] = inj ? bcol[s] : v;
+                    }
+#pragma unroll
+                    for (int s = 0; s < NX; ++s) g[s] = gn[s];
                 }
-#pragma unroll
-                for (int s = 0; s < NX; ++s) g[s] = gn[s];
                 double gf[NXP], yf[NXP];
                 static_for<0, NXP>([&](auto s_c) __attribute__((always_inline)) {
                     constexpr int s = decltype(s_c)::value;
@@ -1602,7 +1668,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
                     const int ci = k * NU + i;
-                    vb[ci] = -rd[ci] - (bpsi3<NX, NU, LS>(sB, yb, k, i) + rho[2 * i] - rho[2 * i + 1]);
+                    vb[ci] = -rd[ci] - (bpsi3<NX, NU, LS, TI>(sB, yb, k, i) + rho[2 * i] - rho[2 * i + 1]);
                 }
             }
             wsync();
@@ -1927,24 +1993,34 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
 #undef ACT
 }
 
-template <int T, int NX, int NU, int NB, bool LS, bool DS, bool L5, bool W2 = false>
+template <int T, int NX, int NU, int NB, bool LS, bool DS, bool L5, bool W2 = false, bool TI = false>
 static hipError_t launch3(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s) {
-    const size_t lds = sizeof(double) * (size_t)lds3_layout<T, NX, NU, NB, LS, DS, W2>(c.N).total;
-    hipError_t e = hipFuncSetAttribute((const void*)mpc_ipm3_kernel<T, NX, NU, NB, LS, DS, L5, W2>,
+    const size_t lds = sizeof(double) * (size_t)lds3_layout<T, NX, NU, NB, LS, DS, W2, TI>(c.N).total;
+    hipError_t e = hipFuncSetAttribute((const void*)mpc_ipm3_kernel<T, NX, NU, NB, LS, DS, L5, W2, TI>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((mpc_ipm3_kernel<T, NX, NU, NB, LS, DS, L5, W2>), dim3(batch), dim3(W2 ? 128 : 64), lds, s,
+    hipLaunchKernelGGL((mpc_ipm3_kernel<T, NX, NU, NB, LS, DS, L5, W2, TI>), dim3(batch), dim3(W2 ? 128 : 64), lds, s,
                        c, p);
     return hipGetLastError();
 }
 
-template <int NX, int NU, int NB, bool LS = false, bool DS = false, bool L5 = false, bool W2 = false>
+// The tile count of the instantiation that runs c: n rounded up to 16 columns, except that three tiles with
+// fewer than four padding columns (n = 45 .. 48: N = 23, 24 at nu = 2) take the four-tile instantiation.  The
+// three-tile one is wrong there: Newton directions off by about 1 % from the first iteration on, agents the C
+// oracle and the generic kernel solve ending at CMPC_UNSOLVED (measured; the cause is not found, n <= 44 agrees
+// with both to 5e-14).  The fourth tile is then all padding (the identity).
+static int mpc3_tiles(const MpcConst& c) {
+    const int t = c.npad / 16;
+    return (t == 3 && c.n > 44) ? 4 : t;
+}
+
+template <int NX, int NU, int NB, bool LS = false, bool DS = false, bool L5 = false, bool W2 = false, bool TI = false>
 static hipError_t launch3_t(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s) {
-    switch (c.npad / 16) {
-        case 1: return launch3<1, NX, NU, NB, LS, DS, L5, W2>(c, p, batch, s);
-        case 2: return launch3<2, NX, NU, NB, LS, DS, L5, W2>(c, p, batch, s);
-        case 3: return launch3<3, NX, NU, NB, LS, DS, L5, W2>(c, p, batch, s);
-        default: return launch3<4, NX, NU, NB, LS, DS, L5, W2>(c, p, batch, s);
+    switch (mpc3_tiles(c)) {
+        case 1: return launch3<1, NX, NU, NB, LS, DS, L5, W2, TI>(c, p, batch, s);
+        case 2: return launch3<2, NX, NU, NB, LS, DS, L5, W2, TI>(c, p, batch, s);
+        case 3: return launch3<3, NX, NU, NB, LS, DS, L5, W2, TI>(c, p, batch, s);
+        default: return launch3<4, NX, NU, NB, LS, DS, L5, W2, TI>(c, p, batch, s);
     }
 }
 
@@ -1956,7 +2032,7 @@ static bool q_diagonal(const MpcConst& c) {
     return true;
 }
 
-// This file is compiled once per instantiation set (CMPC_V3_SET = 1 .. 5; see the Makefile) so
+// This file is compiled once per instantiation set (CMPC_V3_SET = 1 .. 6; see the Makefile) so
 // the instantiations build in parallel.  Set 1 also holds the dispatcher.
 #ifndef CMPC_V3_SET
 #define CMPC_V3_SET 1
@@ -1981,6 +2057,12 @@ static bool q_diagonal(const MpcConst& c) {
                                         : launch3_t<4, 2, NB_, false, true>(c, p, batch, s); \
         return true;                                                                   \
     }
+// ... and the time-invariant instantiation (TI) where the caller promises it (CMPC_FLAG_LTI) in the one-wave mode
+#define CASE_DSTI(NB_)                                                                                        \
+    if (p.fuse.on && c.lti && c.nx == 4 && c.nu == 2 && nb == NB_ && q_diagonal(c) && !mpc3_two_waves(c, batch)) { \
+        *err = launch3_t<4, 2, NB_, false, true, false, false, true>(c, p, batch, s);                        \
+        return true;                                                                                          \
+    }
 #if CMPC_V3_SET == 1
 // Two-wave mode: opt-in (CMPC_FLAG_TWO_WAVES).  Measured at 512 agents on one MI355X (tools/w2_ab.py, 20 cfg3
 // rounds, bit-identical results): 0.646 ms per launch against 0.640 ms with one wave.  Wave 0's K build
@@ -1997,7 +2079,7 @@ size_t mpc3_lds_bytes(const MpcConst& c) {
     if (c.ns != 3 || c.N > 32 || c.mc < 4 || c.n > 64) return 0;
     for (int r = 0; r < c.mc; ++r)
         if (c.row_slack[r] != slk(r) || c.row_sign[r] != (int)sgn(r)) return 0;
-    const int nb = c.mc - 4, T = c.npad / 16;
+    const int nb = c.mc - 4, T = mpc3_tiles(c);
     auto lay = [&](auto nx_c, auto nu_c, auto nb_c, auto ls_c) -> size_t {
         constexpr int NX_ = decltype(nx_c)::value, NU_ = decltype(nu_c)::value, NB_ = decltype(nb_c)::value;
         constexpr bool LS_ = decltype(ls_c)::value;
@@ -2032,6 +2114,7 @@ bool mpc3_try_set2(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s
 bool mpc3_try_set5(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err, int nb);
 bool mpc3_try_set3(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err, int nb);
 bool mpc3_try_set4(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err, int nb);
+bool mpc3_try_set6(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err, int nb);
 
 // Returns true (and launches) when a v3 instantiation covers the problem: PlannerLPV row
 // pattern with nb <= 2 neighbour rows (nb = 3 at nx = 9: the reference's 4-agent case),
@@ -2041,7 +2124,7 @@ bool mpc3_try_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t
     for (int r = 0; r < c.mc; ++r)
         if (c.row_slack[r] != slk(r) || c.row_sign[r] != (int)sgn(r)) return false;
     const int nb = c.mc - 4;
-    if (mpc3_try_set5(c, p, batch, s, err, nb)) return true;
+    if (mpc3_try_set6(c, p, batch, s, err, nb) || mpc3_try_set5(c, p, batch, s, err, nb)) return true;
     CASE(4, 2, 2)
     CASE(4, 2, 1)
     CASE(4, 2, 0)
@@ -2070,6 +2153,13 @@ bool mpc3_try_set5(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s
     CASE_DS(0)
     return false;
 }
+#elif CMPC_V3_SET == 6
+bool mpc3_try_set6(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err, int nb) {
+    CASE_DSTI(2)
+    CASE_DSTI(1)
+    CASE_DSTI(0)
+    return false;
+}
 #else
 bool mpc3_try_set4(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err, int nb) {
     CASE_LS(3)
@@ -2080,5 +2170,6 @@ bool mpc3_try_set4(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s
 #undef CASE
 #undef CASE_LS
 #undef CASE_DS
+#undef CASE_DSTI
 
 }  // namespace cmpc

@@ -16,6 +16,8 @@
 // as its solver call and launch order are queued (its outputs exist whatever the exchange returns), leaves the
 // loop at the first error and synchronises the host once before it returns the error.
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <initializer_list>
 #include <vector>
@@ -154,6 +156,21 @@ hipError_t finish_uploads(RoundsCore* h, hipError_t e) {
         e = hipMemcpyAsync(h->traj_local, h->traj_all + h->traj_row() * h->d.self_offset, own, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e;
+}
+
+// CMPC_FLAG_LTI's condition on a host array of `batch` agents x `N` stages x `per` doubles: every stage of an
+// agent bit-equal to its stage 0 (64-bit patterns: -0.0 is not +0.0), every entry finite
+bool stages_lti(const double* a, size_t batch, size_t N, size_t per) {
+    for (size_t b = 0; b < batch; ++b) {
+        const double* a0 = a + b * N * per;
+        for (size_t i = 0; i < N * per; ++i) {
+            uint64_t u, v;
+            std::memcpy(&u, a0 + i, 8);
+            std::memcpy(&v, a0 + i % per, 8);
+            if (u != v || !std::isfinite(a0[i])) return false;
+        }
+    }
+    return true;
 }
 
 // ---- the parts of a round that both step loops call ----
@@ -523,6 +540,9 @@ int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_m
     h->history = std::max(dims->history, 1);
     const int nx = 2 * prm->dim, nu = prm->dim, mc = 4 + d.nb;
     h->md = cmpc_mpc_dims{nx, nu, d.N, 3, mc, d.batch};
+    // time-invariant agents (the handle never changes A or B after this): the promise the solver may use
+    if (stages_lti(in->A, d.batch, d.N, (size_t)nx * nx) && stages_lti(in->B, d.batch, d.N, (size_t)nx * nu))
+        h->opts.flags |= CMPC_FLAG_LTI;
     std::memcpy(h->Q, w->Q, sizeof(double) * nx * nx);
     std::memcpy(h->R, w->R, sizeof(double) * nu * nu);
     std::memcpy(h->dR, w->dR, sizeof(double) * nu * nu);

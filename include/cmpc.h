@@ -107,8 +107,16 @@ typedef struct cmpc_ctx cmpc_ctx;
                                    fused double-integrator round only (cmpc_di_solve_dev, the DS instantiation);
                                    other solves run one wavefront per agent.  Setting both wave flags is
                                    CMPC_ERR_ARG */
+#define CMPC_FLAG_LTI 2048 /* the caller's promise that every agent of the batch is time-invariant: A_k and B_k are
+                              bit-equal to A_0 and B_0 at every stage (-0.0 is not +0.0), and all are finite.  The
+                              library may then read stage 0 only.  It never checks the promise against device
+                              memory; a batch that breaks it is solved with stage 0's model.  Used by the fused
+                              double-integrator round's one-wave instantiation (cmpc_di_solve_dev /
+                              cmpc_di_round_dev: the condensed dynamics are tabulated once per solve instead of
+                              recomputed in every iteration, bit-identical results); ignored everywhere else.
+                              cmpc_di_rounds_create sets it itself when the host arrays it is given pass the test */
 #define CMPC_FLAG_ALL (CMPC_FLAG_GENERIC | CMPC_FLAG_FP32 | CMPC_FLAG_RICCATI | CMPC_FLAG_RESCUE | CMPC_FLAG_FINISH | \
-                       CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES)
+                       CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES | CMPC_FLAG_LTI)
                        /* other bits: CMPC_ERR_ARG */
 
 typedef struct {

@@ -1,7 +1,8 @@
 """Diagnostic: per-section shader-clock breakdown of the v3 solver kernel.
 Usage: python tools/stamps.py [agents] [N]          cfg3 round-0 problem (double integrator), solved by
                                                     the fused round (rows built in the launch: the
-                                                    bench's path); --unfused: build() + solve()
+                                                    bench's path); --unfused: build() + solve();
+                                                    --no-lti: without CMPC_FLAG_LTI (DIRounds sets it)
        python tools/stamps.py --lpv [round]         bench.py's lpv_rounds population (nx 9) at that
                                                     round (default 6: the slowest of the line)"""
 import os
@@ -31,6 +32,9 @@ for a_, f_ in (("--one-wave", L.CMPC_FLAG_ONE_WAVE), ("--two-waves", L.CMPC_FLAG
     if a_ in sys.argv:
         sys.argv.remove(a_)
         WAVES = f_
+NO_LTI = "--no-lti" in sys.argv
+if NO_LTI:
+    sys.argv.remove("--no-lti")
 LPV = len(sys.argv) > 1 and sys.argv[1] == "--lpv"
 if LPV:
     import bench
@@ -52,10 +56,11 @@ else:
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 30
     sc = S.make_di(n, N, 2, 2)
-    R = DIRounds(sc)
+    R = DIRounds(sc, lti=False if NO_LTI else None)
     R.build()
     if not UNFUSED:
         R.solve = R.build_solve
+    WAVES |= R.opts.flags & L.CMPC_FLAG_LTI
 st = torch.zeros((n, SLOTS), dtype=torch.int64, device="cuda")
 R.opts = L.opts(stamps=st.data_ptr(), flags=WAVES)
 for _ in range(3):
