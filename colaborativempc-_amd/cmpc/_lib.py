@@ -47,6 +47,8 @@ CMPC_FLAG_POLISH = 256  # with RESCUE: active-set polish of breakdowns at the ro
 CMPC_FLAG_ONE_WAVE = 512   # fused DS round: one wavefront per agent (the default)
 CMPC_FLAG_TWO_WAVES = 1024  # ... two wavefronts per agent (opt-in: bit-identical, no faster at 512 agents)
 CMPC_FLAG_LTI = 2048   # the caller's promise: A_k, B_k bit-equal to stage 0's at every stage, all finite (rounds.is_lti)
+CMPC_FLAG_CERTIFY = 4096   # after the solve: status -3 for an agent with a verified Farkas ray (cmpc.infeas)
+CMPC_CERT_TOL = 1e-9       # the certificate's threshold on (reach - h) / S
 
 
 class cmpc_opts(ct.Structure):
@@ -81,6 +83,10 @@ class cmpc_mpc_out(ct.Structure):
 
 class cmpc_mpc_duals(ct.Structure):
     _fields_ = [("y", _DP), ("dua_res", _DP)]
+
+
+class cmpc_mpc_cert(ct.Structure):
+    _fields_ = [("ray", _DP), ("margin", _DP), ("row", _IP)]
 
 
 class cmpc_lpv_params(ct.Structure):
@@ -223,6 +229,10 @@ SIGNATURES = {
                                                   ct.POINTER(cmpc_opts), ct.c_void_p]),
     "cmpc_mpc_duals_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
                                       ct.POINTER(cmpc_mpc_data), _DP, _DP, ct.POINTER(cmpc_mpc_duals), ct.c_void_p]),
+    "cmpc_mpc_certify": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                    ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert)]),
+    "cmpc_mpc_certify_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                        ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert), ct.c_void_p]),
     "cmpc_solve_lpv_batch": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lpv_params), ct.POINTER(cmpc_track),
                                         ct.POINTER(cmpc_lpv_dims), ct.POINTER(cmpc_lpv_data),
                                         ct.POINTER(cmpc_lpv_out), ct.POINTER(cmpc_opts)]),

@@ -68,10 +68,13 @@ def track_of(map_obj):
 class PlannerLPVBatch:
     """All agents of one control step in one GPU call (same gains / map / horizon).
     ``riccati``: force the stage-wise Riccati solver (the default only when N*nu > 64);
-    ``polish``: CMPC_FLAG_POLISH (default on, as the reference's OSQP polish=True)."""
+    ``polish``: CMPC_FLAG_POLISH (default on, as the reference's OSQP polish=True);
+    ``certify``: CMPC_FLAG_CERTIFY: an agent the solver leaves short of status 1 / 2 whose QP has a verified
+    infeasibility certificate (cmpc.infeas: a hard row, the minimum speed, out of the input box's reach) gets
+    OSQP's status -3, on which the reference's loop quits; off by default (one more launch per solve)."""
 
     def __init__(self, Q, Qs, R, dR, N, dt, map, wq=0, model_param=None, sys_lim=None, ctx=None,
-                 tol=None, max_iter=None, riccati=False, polish=True):
+                 tol=None, max_iter=None, riccati=False, polish=True, certify=False):
         self.N, self.dt, self.map = int(N), float(dt), map
         self.ctx = ctx or L.default_context()
         self.prm = lpv_params(Q, Qs, R, dR, dt, wq, model_param, sys_lim)
@@ -80,8 +83,9 @@ class PlannerLPVBatch:
         # saturated rows) is re-solved by the Riccati kernel instead of returning its best iterate;
         # polish on (OSQP's polish=True, LPV_Planner.py:233): a breakdown at the rounding floor has its
         # active set solved exactly
-        self.opts = L.opts(tol, max_iter, L.CMPC_FLAG_RICCATI if riccati else
-                           L.CMPC_FLAG_RESCUE | (L.CMPC_FLAG_POLISH if polish else 0))
+        self.opts = L.opts(tol, max_iter, (L.CMPC_FLAG_RICCATI if riccati else
+                                           L.CMPC_FLAG_RESCUE | (L.CMPC_FLAG_POLISH if polish else 0)) |
+                           (L.CMPC_FLAG_CERTIFY if certify else 0))
 
     def solve(self, x0, x_last, u_last, u_old, x_agents, pose):
         """x0 (B,9); x_last (B,N or N+1,9); u_last (B,N,2); u_old (B,2);
@@ -186,7 +190,7 @@ def feasible_of(status):
 class PlannerLPV:
     """Drop-in for plan_lib.distributedPlanner.PlannerLPV (one agent per call)."""
 
-    def __init__(self, Q, Qs, R, dR, N, dt, map, id, wq=0, model_param=None, sys_lim=None, ctx=None):
+    def __init__(self, Q, Qs, R, dR, N, dt, map, id, wq=0, model_param=None, sys_lim=None, ctx=None, certify=False):
         self.dR, self.n_s, self.slack, self.n_u = dR, N_S, N_SLACK, N_U
         self.n_exp = N_EXP
         self.id, self.dt, self.map, self.N = id, dt, map, N
@@ -205,7 +209,8 @@ class PlannerLPV:
         self.Q, self.Qs, self.R, self.wq = Q, Qs, R, wq
         lim = sys_lim or DEFAULT_LIMITS
         self.min_dist = lim["min_dist"]
-        self._batch = PlannerLPVBatch(Q, Qs, R, dR, N, dt, map, wq, model_param, sys_lim, ctx=ctx)
+        # certify: status -3 (and feasible = 0) where the agent's QP has a verified infeasibility certificate
+        self._batch = PlannerLPVBatch(Q, Qs, R, dR, N, dt, map, wq, model_param, sys_lim, ctx=ctx, certify=certify)
 
     def solve(self, x0, Last_xPredicted, uPred, x_agents, agents_id, pose):
         self.agent_list = agents_id

@@ -96,10 +96,11 @@ def quadprog(H, f, A=None, b=None, Aeq=None, beq=None, lb=None, ub=None, ctx=Non
     return res
 
 
-def _osqp_result(x, y, status_val, text, iters, obj, kkt, pri_res, dua_res, path):
-    res = SimpleNamespace(x=x, y=y, info=SimpleNamespace(status_val=status_val, status=text, iter=iters,
-                                                         obj_val=obj, kkt=kkt, pri_res=pri_res, dua_res=dua_res,
-                                                         solver=path))
+def _osqp_result(x, y, status_val, text, iters, obj, kkt, pri_res, dua_res, path, prim_inf_cert=None):
+    res = SimpleNamespace(x=x, y=y, prim_inf_cert=prim_inf_cert,
+                          info=SimpleNamespace(status_val=status_val, status=text, iter=iters,
+                                               obj_val=obj, kkt=kkt, pri_res=pri_res, dua_res=dua_res,
+                                               solver=path))
     feasible = 1 if status_val in (1, 2, -2) else 0   # LPV_Planner.py:243-249
     if status_val != 1:
         print("OSQP exited with status '%s'" % text)
@@ -133,9 +134,13 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
     reference-form agent QP (LPV_Planner.py:156-157) joins one structured batch per distinct
     shared part (cmpc_solve_mpc_batch: one wavefront per agent); the others go through the
     dense kernel (cmpc_solve_qp_batch; ``structured=False`` sends every QP there).  Returns a
-    list of (res, feasible)."""
+    list of (res, feasible).  A structured QP with a verified infeasibility certificate (cmpc.infeas:
+    a hard row out of the input box's reach) comes back with OSQP's status -3 ("primal infeasible"),
+    feasible = 0 and the Farkas ray in ``res.prim_inf_cert`` (length m + m_eq, OSQP order); every other
+    result has ``prim_inf_cert = None`` (the dense path's -3 carries no ray)."""
     from . import structure as St
-    from .solver import solve_mpc
+    from .infeas import certify_gpu
+    from .solver import PER_AGENT, solve_mpc
 
     recs = [St.recognize(*qp[:6]) if structured else None for qp in qps]
     out = [None] * len(qps)
@@ -149,14 +154,24 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
         # continues on the stage-wise kernel instead of returning CMPC_UNSOLVED (OSQP's -10)
         # res.y: the dual solution in OSQP's order [G rows; A rows] (cmpc.duals; NaN where the solver's exit
         # holds no multipliers of the iterate it returns, never at status 1)
+        # CMPC_FLAG_CERTIFY: OSQP's -3 ("primal infeasible", feasible = 0) for an agent with a verified Farkas
+        # ray; res.prim_inf_cert (OSQP order [G rows; A rows]) from one certificate launch on those agents
         z, kkt, it, st, y, dua = solve_mpc(batch, ctx, tol=tol, max_iter=max_iter, rescue=True, polish=True,
-                                           duals=True)
+                                           duals=True, certify=True)
+        rays = {}
+        bad = np.nonzero(st == L.CMPC_PRIMAL_INFEASIBLE)[0]
+        if bad.size:
+            sub = dict(batch)
+            for k in PER_AGENT:
+                sub[k] = batch[k][bad]
+            c = certify_gpu(sub, ctx=ctx)
+            rays = {int(a): c["ray"][n_] for n_, a in enumerate(bad) if c["row"][n_] >= 0}
         for a, i in enumerate(idx):
             P, q, G, h, A, b = qps[i][:6]
             x = z[a]
             obj = float(0.5 * x @ (P @ x) + np.asarray(q, float) @ x)
             out[i] = _osqp_result(x, y[a], int(st[a]), L.STATUS_TEXT.get(int(st[a]), "unsolved"), int(it[a]), obj,
-                                  float(kkt[a]), _pri_res(x, G, h, A, b), float(dua[a]), "structured")
+                                  float(kkt[a]), _pri_res(x, G, h, A, b), float(dua[a]), "structured", rays.get(a))
     for i, p in enumerate(recs):
         if p is not None:
             continue

@@ -232,6 +232,15 @@ hipError_t mpc_dual_launch(const MpcConst& c, const MpcPtrs& p, const double* z,
                            unsigned long long lam_stride, const double* valid, unsigned long long valid_stride,
                            double* y, double* dua_res, int batch, hipStream_t s);
 
+// Primal-infeasibility certificate (mpc_infeas.hip): single-row reachability over the hard stage rows of every
+// agent whose status (may be null: every agent) is not 1 or 2.  A certified agent's status becomes
+// CMPC_PRIMAL_INFEASIBLE; ray (batch x ny), margin (batch) and row (batch) may be null (cmpc_mpc_cert).  Reads
+// A, B, x0, C, h of `p` only.  The threshold on (reach - h) / S: the sums' rounding is bounded by about
+// (k nx + N nu) 2^-53 S, at most 2e-13 S at the library's largest sizes
+constexpr double kCertTol = CMPC_CERT_TOL;
+hipError_t mpc_infeas_launch(const MpcConst& c, const MpcPtrs& p, int* status, double* ray, double* margin, int* row,
+                             int batch, hipStream_t s);
+
 // LPV reference-semantics builder (scheduling + planes + weights + rows).
 struct LpvConst {
     int N, nb, last_rows, nseg, mc;

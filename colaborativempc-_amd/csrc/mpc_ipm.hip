@@ -820,8 +820,19 @@ static hipError_t launch_t(const MpcConst& c, const MpcPtrs& p, int batch, hipSt
     return hipGetLastError();
 }
 
-hipError_t mpc_launch(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags) {
+static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags);
+
+hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, int flags) {
     if (batch == 0) return hipSuccess;
+    const hipError_t e = solve_launches(c, p, batch, s, flags);
+    // certificate (CMPC_FLAG_CERTIFY) last, behind every solver path: it reads the problem data and the final
+    // statuses only; the fused double-integrator round keeps its rows in LDS only, so it has none to certify
+    // against (as the polish below)
+    if (e != hipSuccess || !(flags & CMPC_FLAG_CERTIFY) || !p.status || p.fuse.on) return e;
+    return mpc_infeas_launch(c, p, p.status, nullptr, nullptr, nullptr, batch, s);
+}
+
+static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags) {
     MpcConst c = c_in;
     c.ws_stride = p.ws ? mpc_ws_doubles(c) : 0;
     if (c.duals && (!p.ws || c.lane || c.f32)) return hipErrorInvalidValue;

@@ -49,7 +49,8 @@ extern "C" {
                                 cmpc_nbr_select_dev, CMPC_ROUNDS_RESELECT; cmpc_order_by_iters_dev,
                                 cmpc_di_rounds_*, CMPC_ROUNDS_LPT; cmpc_round_log_dev,
                                 cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, CMPC_LOG_SEPARATION;
-                                cmpc_mpc_duals, cmpc_solve_mpc_batch_duals[_dev], cmpc_mpc_duals_dev */
+                                cmpc_mpc_duals, cmpc_solve_mpc_batch_duals[_dev], cmpc_mpc_duals_dev;
+                                CMPC_FLAG_CERTIFY, cmpc_mpc_cert, cmpc_mpc_certify[_dev] */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -115,8 +116,21 @@ typedef struct cmpc_ctx cmpc_ctx;
                               cmpc_di_round_dev: the condensed dynamics are tabulated once per solve instead of
                               recomputed in every iteration, bit-identical results); ignored everywhere else.
                               cmpc_di_rounds_create sets it itself when the host arrays it is given pass the test */
+#define CMPC_FLAG_CERTIFY 4096 /* after the solve and every rescue / polish launch, the infeasibility certificate
+                                  (cmpc_mpc_certify_dev below, one more launch) runs on the agents whose status is not
+                                  1 or 2: an agent with a verified Farkas ray gets status CMPC_PRIMAL_INFEASIBLE (OSQP's
+                                  -3; the reference's loop quits on it, LPV_Planner.py:243-249).  z, kkt, iters of every
+                                  agent and the status of every uncertified agent are bit-identical to the call without
+                                  the flag (the kernel reads problem data and status only), behind every solver path.
+                                  Honoured by cmpc_solve_mpc_batch[_dev], cmpc_solve_mpc_batch_duals[_dev],
+                                  cmpc_solve_lpv_batch[_dev] (on the builder's rows) and so by both round handles:
+                                  cmpc_lpv_rounds_step halts on -3 as on any infeasible status.  Ignored where the
+                                  fused double-integrator round keeps its rows in LDS only (cmpc_di_solve_dev /
+                                  cmpc_di_round_dev on a v3 instantiation: no rows in memory to certify against, as for
+                                  CMPC_FLAG_POLISH there) and when out->status is NULL */
 #define CMPC_FLAG_ALL (CMPC_FLAG_GENERIC | CMPC_FLAG_FP32 | CMPC_FLAG_RICCATI | CMPC_FLAG_RESCUE | CMPC_FLAG_FINISH | \
-                       CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES | CMPC_FLAG_LTI)
+                       CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES | CMPC_FLAG_LTI | \
+                       CMPC_FLAG_CERTIFY)
                        /* other bits: CMPC_ERR_ARG */
 
 typedef struct {
@@ -244,6 +258,53 @@ int cmpc_solve_mpc_batch_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, con
 int cmpc_mpc_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                        const cmpc_mpc_data* dev_in, const double* z, const double* lam,
                        const cmpc_mpc_duals* dev_duals, void* hip_stream);
+
+/* Primal-infeasibility certificate of the same QP: OSQP's status -3 with its res.prim_inf_cert, for the structured
+ * solves.  -3 is only ever reported with a ray that has been verified, never on a heuristic.
+ *
+ * Single-row reachability.  A hard stage row (k, r), k = 1..N, with row_slack[r] == -1 and finite h_{k,r}, asks
+ * c'x_k <= h with c = C_{k,r}.  The adjoint recursion p_k = c, g_j = B_j' p_{j+1}, p_j = A_j' p_{j+1} (j = k-1 .. 0)
+ * gives c'x_k = p_0'x0 + sum_j g_j'u_j, so the smallest value the row can take over the input box is
+ *   reach = p_0'x0 + sum_{j<k, i} min(g_ji lb_i, g_ji ub_i)
+ * (a term with g_ji == 0 counts 0; a term whose minimising bound is infinite disqualifies the row).  With
+ *   S = |h| + sum_s |p_0s x0_s| + sum_{j,i} |g_ji| |the minimising bound|
+ * the QP is infeasible when reach - h > CMPC_CERT_TOL * S.  The rounding of these sums is bounded by about
+ * (k nx + N nu) 2^-53 S, at most 2e-13 S at the library's largest sizes, so 1e-9 leaves three orders of margin.
+ * Among an agent's candidate rows the largest (reach - h) / S wins, ties to the smallest k, then r; a candidate
+ * with a non-finite ratio (NaN or infinite data) is no candidate.  u_lb_i > u_ub_i for any input: no certificate
+ * is attempted.
+ *
+ * The Farkas ray in the layout of cmpc_mpc_duals.y ([y_G | y_A], ny = m + (nx+ns)(N+1) + nu N):
+ *   y_G   1 at row (k, r); for j < k and input i, t = -g_ji: t on the u_i <= ub_i row when t > 0, -t on the
+ *         -u_i <= -lb_i row when t < 0; 0 elsewhere
+ *   y_A   nu_j = -p_j on the state rows j <= k, 0 beyond; 0 on the slack rows and the input-rate rows
+ * so that G'y_G + A'y_A = 0 and h'y_G + b'y_A = -(reach - h) < 0 by construction.
+ *
+ * The certificate is sufficient, not necessary: infeasibility that needs two or more rows combined (or a soft
+ * row, which a slack always satisfies) gets no certificate, and such an agent's status stays what the solver
+ * gave.  Out of scope: rays from the solver's diverging multipliers (the general case); a pre-solve screen
+ * that spares infeasible agents their iterations (it would change iters); the MEX gateways.
+ *
+ * cmpc_mpc_certify_dev: DEVICE pointers, one launch, graph-capturable, one wavefront per agent; of dev_in it reads
+ * A, B, x0, C and h.  status (in-out, may be NULL): an agent at CMPC_SOLVED or CMPC_SOLVED_INACCURATE is skipped
+ * (none of its outputs is written); a certified agent's status becomes CMPC_PRIMAL_INFEASIBLE; NULL: every agent
+ * is examined.  For an examined agent: margin = the best candidate's (reach - h) / S, NaN without a candidate;
+ * row = (k-1) mc + r when certified, else -1; the ray row as above when certified, else all NaN.
+ * cmpc_mpc_certify: the same with HOST pointers (status, ray, margin, row are copied in and out, so a skipped
+ * agent keeps what the caller put there).
+ * CMPC_ERR_ARG: NULL dims, w or in, or status and cert both NULL; dimension checks as cmpc_solve_mpc_batch.
+ * batch == 0: CMPC_OK without a launch. */
+#define CMPC_CERT_TOL 1e-9
+typedef struct {
+    double* ray;     /* batch x ny, may be NULL */
+    double* margin;  /* batch, may be NULL */
+    int* row;        /* batch, may be NULL */
+} cmpc_mpc_cert;
+
+int cmpc_mpc_certify(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                     const cmpc_mpc_data* host_in, int* status, const cmpc_mpc_cert* host_cert);
+int cmpc_mpc_certify_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                         const cmpc_mpc_data* dev_in, int* status, const cmpc_mpc_cert* dev_cert, void* hip_stream);
 
 /* The solver a structured batch would run, and how many of its workgroups share a CU — host only
  * (no context, no device).  Every solver uses more than 256 VGPRs + AGPRs per lane, so one
