@@ -49,6 +49,19 @@ CMPC_FLAG_TWO_WAVES = 1024  # ... two wavefronts per agent (opt-in: bit-identica
 CMPC_FLAG_LTI = 2048   # the caller's promise: A_k, B_k bit-equal to stage 0's at every stage, all finite (rounds.is_lti)
 CMPC_FLAG_CERTIFY = 4096   # after the solve: status -3 for an agent with a verified Farkas ray (cmpc.infeas)
 CMPC_CERT_TOL = 1e-9       # the certificate's threshold on (reach - h) / S
+CMPC_FLAG_CERTIFY_ROWS = 8192   # with CERTIFY: then the combined-row certificate on the agents still short of 1, 2, -3
+CMPC_CERT_ROWS_MAX_ITER = 512   # the combined-row certificate's iteration cap ...
+CMPC_CERT_ROWS_CHECK_EVERY = 8  # ... and the iterations between two of its reachability checks
+
+
+def certify_flags(certify):
+    """The flag bits of a wrapper's ``certify`` argument: False: none; True: CMPC_FLAG_CERTIFY (the single-row
+    rule); "rows": CMPC_FLAG_CERTIFY_ROWS as well (then the combined-row rule on the agents it leaves)."""
+    if isinstance(certify, str):
+        if certify != "rows":
+            raise ValueError(f"certify: True, False or 'rows', not {certify!r}")
+        return CMPC_FLAG_CERTIFY | CMPC_FLAG_CERTIFY_ROWS
+    return CMPC_FLAG_CERTIFY if certify else 0
 
 
 class cmpc_opts(ct.Structure):
@@ -87,6 +100,10 @@ class cmpc_mpc_duals(ct.Structure):
 
 class cmpc_mpc_cert(ct.Structure):
     _fields_ = [("ray", _DP), ("margin", _DP), ("row", _IP)]
+
+
+class cmpc_mpc_cert_rows(ct.Structure):
+    _fields_ = [("ray", _DP), ("margin", _DP), ("iters", _IP), ("nrows", _IP)]
 
 
 class cmpc_lpv_params(ct.Structure):
@@ -233,6 +250,12 @@ SIGNATURES = {
                                     ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert)]),
     "cmpc_mpc_certify_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
                                         ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert), ct.c_void_p]),
+    "cmpc_mpc_certify_rows": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                         ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert_rows), ct.c_int,
+                                         ct.c_int]),
+    "cmpc_mpc_certify_rows_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                             ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert_rows),
+                                             ct.c_int, ct.c_int, ct.c_void_p]),
     "cmpc_solve_lpv_batch": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lpv_params), ct.POINTER(cmpc_track),
                                         ct.POINTER(cmpc_lpv_dims), ct.POINTER(cmpc_lpv_data),
                                         ct.POINTER(cmpc_lpv_out), ct.POINTER(cmpc_opts)]),

@@ -71,7 +71,9 @@ class PlannerLPVBatch:
     ``polish``: CMPC_FLAG_POLISH (default on, as the reference's OSQP polish=True);
     ``certify``: CMPC_FLAG_CERTIFY: an agent the solver leaves short of status 1 / 2 whose QP has a verified
     infeasibility certificate (cmpc.infeas: a hard row, the minimum speed, out of the input box's reach) gets
-    OSQP's status -3, on which the reference's loop quits; off by default (one more launch per solve)."""
+    OSQP's status -3, on which the reference's loop quits; off by default (one more launch per solve);
+    ``certify="rows"``: CMPC_FLAG_CERTIFY_ROWS as well (hard rows that contradict each other, cmpc.infeas.certify_rows;
+    one more launch)."""
 
     def __init__(self, Q, Qs, R, dR, N, dt, map, wq=0, model_param=None, sys_lim=None, ctx=None,
                  tol=None, max_iter=None, riccati=False, polish=True, certify=False):
@@ -85,7 +87,7 @@ class PlannerLPVBatch:
         # active set solved exactly
         self.opts = L.opts(tol, max_iter, (L.CMPC_FLAG_RICCATI if riccati else
                                            L.CMPC_FLAG_RESCUE | (L.CMPC_FLAG_POLISH if polish else 0)) |
-                           (L.CMPC_FLAG_CERTIFY if certify else 0))
+                           L.certify_flags(certify))
 
     def solve(self, x0, x_last, u_last, u_old, x_agents, pose):
         """x0 (B,9); x_last (B,N or N+1,9); u_last (B,N,2); u_old (B,2);

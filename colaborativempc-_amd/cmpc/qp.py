@@ -128,7 +128,7 @@ def _dua_res(x, y, P, q, G, A):
     return float(np.abs(np.asarray(r).ravel()).max(initial=0.0))
 
 
-def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True):
+def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True, certify_rows=False):
     """Many ``osqp_solve_qp`` calls in as few GPU launches as possible: ``qps`` is a list of
     (P, q, G, h, A, b) tuples.  Every QP that ``structure.recognize`` identifies as a
     reference-form agent QP (LPV_Planner.py:156-157) joins one structured batch per distinct
@@ -137,9 +137,11 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
     list of (res, feasible).  A structured QP with a verified infeasibility certificate (cmpc.infeas:
     a hard row out of the input box's reach) comes back with OSQP's status -3 ("primal infeasible"),
     feasible = 0 and the Farkas ray in ``res.prim_inf_cert`` (length m + m_eq, OSQP order); every other
-    result has ``prim_inf_cert = None`` (the dense path's -3 carries no ray)."""
+    result has ``prim_inf_cert = None`` (the dense path's -3 carries no ray).  ``certify_rows``: the combined-row
+    certificate as well (CMPC_FLAG_CERTIFY_ROWS, cmpc.infeas.certify_rows: hard rows that are each reachable alone
+    but contradict each other), with its ray in ``res.prim_inf_cert``; off, the adapter is what it is without it."""
     from . import structure as St
-    from .infeas import certify_gpu
+    from .infeas import certify_gpu, certify_rows_gpu
     from .solver import PER_AGENT, solve_mpc
 
     recs = [St.recognize(*qp[:6]) if structured else None for qp in qps]
@@ -157,7 +159,7 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
         # CMPC_FLAG_CERTIFY: OSQP's -3 ("primal infeasible", feasible = 0) for an agent with a verified Farkas
         # ray; res.prim_inf_cert (OSQP order [G rows; A rows]) from one certificate launch on those agents
         z, kkt, it, st, y, dua = solve_mpc(batch, ctx, tol=tol, max_iter=max_iter, rescue=True, polish=True,
-                                           duals=True, certify=True)
+                                           duals=True, certify="rows" if certify_rows else True)
         rays = {}
         bad = np.nonzero(st == L.CMPC_PRIMAL_INFEASIBLE)[0]
         if bad.size:
@@ -166,6 +168,12 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
                 sub[k] = batch[k][bad]
             c = certify_gpu(sub, ctx=ctx)
             rays = {int(a): c["ray"][n_] for n_, a in enumerate(bad) if c["row"][n_] >= 0}
+            left = np.array([n_ for n_ in range(bad.size) if c["row"][n_] < 0], int)
+            if certify_rows and left.size:   # the agents the single-row launch left: the combined-row ray
+                for k in PER_AGENT:
+                    sub[k] = batch[k][bad[left]]
+                c = certify_rows_gpu(sub, ctx=ctx)
+                rays.update({int(bad[left[n_]]): c["ray"][n_] for n_ in range(left.size) if c["status"][n_] == -3})
         for a, i in enumerate(idx):
             P, q, G, h, A, b = qps[i][:6]
             x = z[a]
@@ -188,7 +196,7 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True)
     return out
 
 
-def osqp_solve_qp(P, q, G=None, h=None, A=None, b=None, initvals=None, ctx=None):
+def osqp_solve_qp(P, q, G=None, h=None, A=None, b=None, initvals=None, ctx=None, certify_rows=False):
     """Drop-in for the reference's ``osqp_solve_qp`` (LPV_Planner.py:192-249): the same QP
     (min 1/2 x'Px + q'x s.t. G x <= h, A x = b) solved on the GPU, returning (res, feasible)
     with ``res.x``, ``res.info.status_val`` / ``.status`` (OSQP codes), ``.obj_val``, ``.iter``,
@@ -197,5 +205,5 @@ def osqp_solve_qp(P, q, G=None, h=None, A=None, b=None, initvals=None, ctx=None)
     QP and solved by the structured kernels, "dense" otherwise).  ``initvals`` is accepted
     but unused: the reference passes it to ``osqp.warm_start`` (:237-238), while the
     interior-point method here starts from its own interior point (the caller in the
-    reference, PlannerLPV.solve :156-157, never passes it)."""
-    return osqp_solve_qp_batch([(P, q, G, h, A, b)], ctx=ctx)[0]
+    reference, PlannerLPV.solve :156-157, never passes it).  ``certify_rows``: as ``osqp_solve_qp_batch``."""
+    return osqp_solve_qp_batch([(P, q, G, h, A, b)], ctx=ctx, certify_rows=certify_rows)[0]

@@ -55,7 +55,7 @@ def _flags(fp32=False, riccati=False, generic=False, rescue=False, lane=False, p
     return (L.CMPC_FLAG_FP32 if fp32 else 0) | (L.CMPC_FLAG_RICCATI if riccati else 0) | \
         (L.CMPC_FLAG_GENERIC if generic else 0) | (L.CMPC_FLAG_RESCUE if rescue else 0) | \
         (L.CMPC_FLAG_LANE if lane else 0) | (L.CMPC_FLAG_POLISH if polish else 0) | \
-        (L.CMPC_FLAG_CERTIFY if certify else 0)
+        L.certify_flags(certify)
 
 
 def plan(shared, batch=1, fp32=False, riccati=False, generic=False, lane=False, rescue=False, polish=False, flags=0):
@@ -99,7 +99,8 @@ def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, g
     fp32 and lane paths have none (CmpcError, CMPC_ERR_UNSUPPORTED);
     ``certify``: CMPC_FLAG_CERTIFY: after the solve, an agent whose status is not 1 or 2 and that has a verified
     Farkas ray (cmpc.infeas: single-row reachability) gets status CMPC_PRIMAL_INFEASIBLE (-3); z, kkt, iters and
-    every other status are bit-identical to the call without it;
+    every other status are bit-identical to the call without it; ``certify="rows"``: CMPC_FLAG_CERTIFY_ROWS as
+    well: then the combined-row certificate (cmpc.infeas.certify_rows) on the agents still short of 1, 2 and -3;
     ``flags``: further CMPC_FLAG_* bits.
 
     Returns (z (B,nz), kkt (B,), iters (B,), status (B,)), with ``duals`` (z, kkt, iters, status, y, dua_res)."""
@@ -153,7 +154,7 @@ def solve_mpc_dev(shared, dev, out, ctx=None, tol=None, max_iter=None, stream=No
     'z' (float64) and optional 'kkt' (float64), 'iters', 'status' (int32) tensors; with a 'y' tensor
     (float64, B x cmpc.duals.ny_of) and optionally 'dua_res' (float64, B) the dual solution is written too
     (cmpc_solve_mpc_batch_duals_dev, one more launch on the same stream).  ``certify``: CMPC_FLAG_CERTIFY (needs
-    out['status']; one more launch).
+    out['status']; one more launch); ``"rows"``: CMPC_FLAG_CERTIFY_ROWS as well (one more).
     Launches asynchronously on ``stream`` (default: torch's current stream)."""
     import torch
 

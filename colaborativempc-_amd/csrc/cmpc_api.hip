@@ -352,6 +352,79 @@ int cmpc_mpc_certify(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weigh
     return CMPC_OK;
 }
 
+int cmpc_mpc_certify_rows_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                              const cmpc_mpc_data* in, int* status, const cmpc_mpc_cert_rows* cert, int max_iter,
+                              int check_every, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!dims || !w || !in || (!status && !cert)) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::MpcConst c;
+    const char* msg = nullptr;
+    int rc = cmpc::mpc_prepare(dims, w, nullptr, &c, &msg);
+    if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (dims->batch == 0) return CMPC_OK;
+    if (!in->A || !in->B || !in->x0 || (c.ms && (!in->C || !in->h))) return fail(ctx, CMPC_ERR_ARG, "null data");
+    if (cmpc::mpc_infeas_rows_lds_bytes(c) > cmpc::kMaxLdsBytes)
+        return fail(ctx, CMPC_ERR_UNSUPPORTED, "the iterates of this horizon do not fit the certificate's 160 KB of LDS");
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    cmpc::MpcPtrs p{in->A, in->B, in->x0, nullptr, nullptr, in->C, in->h, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr};
+    HIP_TRY(cmpc::mpc_infeas_rows_launch(c, p, status, cert ? cert->ray : nullptr, cert ? cert->margin : nullptr,
+                                         cert ? cert->iters : nullptr, cert ? cert->nrows : nullptr, max_iter,
+                                         check_every, dims->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
+int cmpc_mpc_certify_rows(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                          int* status, const cmpc_mpc_cert_rows* cert, int max_iter, int check_every) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!d || !w || !in || (!status && !cert)) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::MpcConst c;
+    const char* msg = nullptr;
+    int rc = cmpc::mpc_prepare(d, w, nullptr, &c, &msg);
+    if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (d->batch == 0) return CMPC_OK;
+    if (!in->A || !in->B || !in->x0 || (c.ms && (!in->C || !in->h))) return fail(ctx, CMPC_ERR_ARG, "null data");
+    if (cmpc::mpc_infeas_rows_lds_bytes(c) > cmpc::kMaxLdsBytes)
+        return fail(ctx, CMPC_ERR_UNSUPPORTED, "the iterates of this horizon do not fit the certificate's 160 KB of LDS");
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    const size_t B = d->batch, N = d->N, nx = d->nx, nu = d->nu, mc = d->mc;
+    const size_t sA = B * N * nx * nx, sB = B * N * nx * nu, sx = B * nx, sC = B * N * mc * nx, sh = B * N * mc;
+    double* hray = cert ? cert->ray : nullptr;
+    double* hmar = cert ? cert->margin : nullptr;
+    int* hit = cert ? cert->iters : nullptr;
+    int* hnr = cert ? cert->nrows : nullptr;
+    const size_t sy = hray ? B * ((size_t)c.m + (size_t)(d->nx + d->ns) * (N + 1) + nu * N) : 0;
+    char* base = arena(ctx, 8 * (sA + sB + sx + sC + sh + sy + B) + 12 * B + 11 * 256);
+    if (!base) return fail(ctx, CMPC_ERR_NOMEM, "device arena allocation failed");
+    Carve cv{base};
+    double *dA = cv.take<double>(sA), *dB = cv.take<double>(sB), *dx0 = cv.take<double>(sx),
+           *dC = cv.take<double>(sC), *dh = cv.take<double>(sh), *dy = cv.take<double>(sy),
+           *dm = cv.take<double>(B);
+    int *ds = cv.take<int>(B), *di = cv.take<int>(B), *dn = cv.take<int>(B);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dA, in->A, 8 * sA, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dB, in->B, 8 * sB, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dx0, in->x0, 8 * sx, hipMemcpyHostToDevice, s));
+    if (sC) HIP_TRY(hipMemcpyAsync(dC, in->C, 8 * sC, hipMemcpyHostToDevice, s));
+    if (sh) HIP_TRY(hipMemcpyAsync(dh, in->h, 8 * sh, hipMemcpyHostToDevice, s));
+    // the outputs go in as well as out: a skipped agent (status 1, 2 or -3) keeps what the caller put there
+    if (status) HIP_TRY(hipMemcpyAsync(ds, status, 4 * B, hipMemcpyHostToDevice, s));
+    if (hray) HIP_TRY(hipMemcpyAsync(dy, hray, 8 * sy, hipMemcpyHostToDevice, s));
+    if (hmar) HIP_TRY(hipMemcpyAsync(dm, hmar, 8 * B, hipMemcpyHostToDevice, s));
+    if (hit) HIP_TRY(hipMemcpyAsync(di, hit, 4 * B, hipMemcpyHostToDevice, s));
+    if (hnr) HIP_TRY(hipMemcpyAsync(dn, hnr, 4 * B, hipMemcpyHostToDevice, s));
+    cmpc::MpcPtrs p{dA, dB, dx0, nullptr, nullptr, dC, dh, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    HIP_TRY(cmpc::mpc_infeas_rows_launch(c, p, status ? ds : nullptr, hray ? dy : nullptr, hmar ? dm : nullptr,
+                                         hit ? di : nullptr, hnr ? dn : nullptr, max_iter, check_every, d->batch, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, ds, 4 * B, hipMemcpyDeviceToHost, s));
+    if (hray) HIP_TRY(hipMemcpyAsync(hray, dy, 8 * sy, hipMemcpyDeviceToHost, s));
+    if (hmar) HIP_TRY(hipMemcpyAsync(hmar, dm, 8 * B, hipMemcpyDeviceToHost, s));
+    if (hit) HIP_TRY(hipMemcpyAsync(hit, di, 4 * B, hipMemcpyDeviceToHost, s));
+    if (hnr) HIP_TRY(hipMemcpyAsync(hnr, dn, 4 * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
 int cmpc_plan_mpc(const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_opts* opts, cmpc_plan_info* out) {
     if (!dims || !w || !out) return CMPC_ERR_ARG;
     cmpc::MpcConst c;

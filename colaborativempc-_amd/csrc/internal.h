@@ -241,6 +241,13 @@ constexpr double kCertTol = CMPC_CERT_TOL;
 hipError_t mpc_infeas_launch(const MpcConst& c, const MpcPtrs& p, int* status, double* ray, double* margin, int* row,
                              int batch, hipStream_t s);
 
+// Combined-row certificate (mpc_infeas_rows.hip): the agents whose status (may be null: every agent) is not 1, 2 or
+// -3.  ray (batch x ny), margin, iters, nrows (batch) may be null (cmpc_mpc_cert_rows); max_iter / check_every <= 0:
+// the library's defaults.  Reads A, B, x0, C, h of `p` only.  hipErrorInvalidValue when the iterates do not fit LDS
+size_t mpc_infeas_rows_lds_bytes(const MpcConst& c);
+hipError_t mpc_infeas_rows_launch(const MpcConst& c, const MpcPtrs& p, int* status, double* ray, double* margin,
+                                  int* iters, int* nrows, int max_iter, int check_every, int batch, hipStream_t s);
+
 // LPV reference-semantics builder (scheduling + planes + weights + rows).
 struct LpvConst {
     int N, nb, last_rows, nseg, mc;

@@ -19,6 +19,7 @@
 // with p = c.  p and the two accumulators stay in registers (static indices only).  Winner: the largest
 // (reach - h) / S, ties to the smallest q (k, then r).  A candidate with a non-finite ratio (NaN or infinite
 // data) is no candidate: NaN never wins a comparison.  Every element of the ray row is written exactly once.
+#include "infeas_ops.h"
 #include "internal.h"
 #include "wave_ops.h"
 
@@ -36,43 +37,6 @@ struct CertPtrs {
     double* margin;  // optional
     int* row;        // optional
 };
-
-// g = B_j' p, then p <- A_j' p where `on`
-__device__ __forceinline__ void adjoint_step(int nx, int nu, const double* __restrict__ Aj,
-                                             const double* __restrict__ Bj, double (&p)[CMPC_MAX_NX],
-                                             double (&g)[CMPC_MAX_NU], bool on) {
-    double pn[CMPC_MAX_NX];
-#pragma unroll
-    for (int t = 0; t < CMPC_MAX_NX; ++t) pn[t] = 0.0;
-#pragma unroll
-    for (int i = 0; i < CMPC_MAX_NU; ++i) g[i] = 0.0;
-#pragma unroll
-    for (int s = 0; s < CMPC_MAX_NX; ++s) {
-        if (s < nx) {
-            const double ps = p[s];
-#pragma unroll
-            for (int i = 0; i < CMPC_MAX_NU; ++i)
-                if (i < nu) g[i] = fma(Bj[s * nu + i], ps, g[i]);
-#pragma unroll
-            for (int t = 0; t < CMPC_MAX_NX; ++t)
-                if (t < nx) pn[t] = fma(Aj[s * nx + t], ps, pn[t]);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < CMPC_MAX_NX; ++t) p[t] = on ? pn[t] : p[t];
-}
-
-// the r of the jr-th hard row (row_slack < 0)
-__device__ __forceinline__ int hard_row(const MpcConst& c, int jr) {
-    int r = 0, cnt = 0;
-    for (int rr = 0; rr < c.mc; ++rr) {
-        if (c.row_slack[rr] < 0) {
-            r = cnt == jr ? rr : r;
-            ++cnt;
-        }
-    }
-    return r;
-}
 
 __global__ __launch_bounds__(kWave) void mpc_infeas_kernel(const MpcConst c, const CertPtrs P) {
     const int lane = threadIdx.x;

@@ -720,6 +720,10 @@ int mpc_prepare(const cmpc_mpc_dims* d, const cmpc_mpc_weights* wt, const cmpc_o
         *msg = "unknown bits in opts.flags";
         return CMPC_ERR_ARG;
     }
+    if (o && (o->flags & CMPC_FLAG_CERTIFY_ROWS) && !(o->flags & CMPC_FLAG_CERTIFY)) {
+        *msg = "CMPC_FLAG_CERTIFY_ROWS needs CMPC_FLAG_CERTIFY";
+        return CMPC_ERR_ARG;
+    }
     const bool fp32 = o && (o->flags & CMPC_FLAG_FP32);
     const bool lane_req = o && (o->flags & CMPC_FLAG_LANE);
     *c = MpcConst{};
@@ -829,7 +833,11 @@ hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_
     // statuses only; the fused double-integrator round keeps its rows in LDS only, so it has none to certify
     // against (as the polish below)
     if (e != hipSuccess || !(flags & CMPC_FLAG_CERTIFY) || !p.status || p.fuse.on) return e;
-    return mpc_infeas_launch(c, p, p.status, nullptr, nullptr, nullptr, batch, s);
+    const hipError_t e1 = mpc_infeas_launch(c, p, p.status, nullptr, nullptr, nullptr, batch, s);
+    // ... then the combined-row certificate (CMPC_FLAG_CERTIFY_ROWS) on the agents still short of 1, 2 and -3; a
+    // horizon whose iterates do not fit its LDS keeps the single-row statuses
+    if (e1 != hipSuccess || !(flags & CMPC_FLAG_CERTIFY_ROWS) || mpc_infeas_rows_lds_bytes(c) > kMaxLdsBytes) return e1;
+    return mpc_infeas_rows_launch(c, p, p.status, nullptr, nullptr, nullptr, nullptr, 0, 0, batch, s);
 }
 
 static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags) {

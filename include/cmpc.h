@@ -50,7 +50,8 @@ extern "C" {
                                 cmpc_di_rounds_*, CMPC_ROUNDS_LPT; cmpc_round_log_dev,
                                 cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, CMPC_LOG_SEPARATION;
                                 cmpc_mpc_duals, cmpc_solve_mpc_batch_duals[_dev], cmpc_mpc_duals_dev;
-                                CMPC_FLAG_CERTIFY, cmpc_mpc_cert, cmpc_mpc_certify[_dev] */
+                                CMPC_FLAG_CERTIFY, cmpc_mpc_cert, cmpc_mpc_certify[_dev];
+                                CMPC_FLAG_CERTIFY_ROWS, cmpc_mpc_cert_rows, cmpc_mpc_certify_rows[_dev] */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -128,9 +129,17 @@ typedef struct cmpc_ctx cmpc_ctx;
                                   fused double-integrator round keeps its rows in LDS only (cmpc_di_solve_dev /
                                   cmpc_di_round_dev on a v3 instantiation: no rows in memory to certify against, as for
                                   CMPC_FLAG_POLISH there) and when out->status is NULL */
+#define CMPC_FLAG_CERTIFY_ROWS 8192 /* with CMPC_FLAG_CERTIFY (alone: CMPC_ERR_ARG): after the single-row launch, the
+                                       combined-row certificate (cmpc_mpc_certify_rows_dev below, one more launch,
+                                       CMPC_CERT_ROWS_MAX_ITER / CMPC_CERT_ROWS_CHECK_EVERY) runs on the agents whose
+                                       status is still not 1, 2 or -3: hard rows that are each reachable alone but
+                                       contradict each other.  Same conditions, same guarantee: z, kkt, iters of
+                                       every agent and the status of every uncertified agent are bit-identical to
+                                       the call without the flag.  A horizon whose iterates do not fit the
+                                       certificate's LDS (cmpc_mpc_certify_rows) keeps the single-row statuses */
 #define CMPC_FLAG_ALL (CMPC_FLAG_GENERIC | CMPC_FLAG_FP32 | CMPC_FLAG_RICCATI | CMPC_FLAG_RESCUE | CMPC_FLAG_FINISH | \
                        CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES | CMPC_FLAG_LTI | \
-                       CMPC_FLAG_CERTIFY)
+                       CMPC_FLAG_CERTIFY | CMPC_FLAG_CERTIFY_ROWS)
                        /* other bits: CMPC_ERR_ARG */
 
 typedef struct {
@@ -281,9 +290,10 @@ int cmpc_mpc_duals_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_
  * so that G'y_G + A'y_A = 0 and h'y_G + b'y_A = -(reach - h) < 0 by construction.
  *
  * The certificate is sufficient, not necessary: infeasibility that needs two or more rows combined (or a soft
- * row, which a slack always satisfies) gets no certificate, and such an agent's status stays what the solver
- * gave.  Out of scope: rays from the solver's diverging multipliers (the general case); a pre-solve screen
- * that spares infeasible agents their iterations (it would change iters); the MEX gateways.
+ * row, which a slack always satisfies) gets no certificate from this rule, and such an agent's status stays what
+ * the solver gave; the combined-row certificate below (cmpc_mpc_cert_rows) covers several hard rows combined.  Out
+ * of scope: rays from the solver's diverging multipliers; a pre-solve screen that spares infeasible agents their
+ * iterations (it would change iters); the MEX gateways.
  *
  * cmpc_mpc_certify_dev: DEVICE pointers, one launch, graph-capturable, one wavefront per agent; of dev_in it reads
  * A, B, x0, C and h.  status (in-out, may be NULL): an agent at CMPC_SOLVED or CMPC_SOLVED_INACCURATE is skipped
@@ -305,6 +315,64 @@ int cmpc_mpc_certify(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_we
                      const cmpc_mpc_data* host_in, int* status, const cmpc_mpc_cert* host_cert);
 int cmpc_mpc_certify_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                          const cmpc_mpc_data* dev_in, int* status, const cmpc_mpc_cert* dev_cert, void* hip_stream);
+
+/* Combined-row certificate: primal infeasibility that needs several hard rows combined (a hard corridor
+ * c'x_k <= h1, -c'x_k <= -h2 with h2 > h1; two hard planes pinching), each row reachable alone.  As above, -3 is only
+ * ever reported with a ray the library has verified; an iteration only proposes the row weights.
+ *
+ * H is the set of hard stage rows (row_slack[r] == -1) of finite h.  No candidate (NaN margin, 0 iterations) when H
+ * is empty or u_lb_i > u_ub_i for any input.  H, the dynamics and the input box are infeasible together exactly when
+ * the least-squares violation  min over the box of 1/2 ||(C x(u) - h)_+||^2  is positive, and at its minimiser the
+ * violation vector is a Farkas ray.
+ *   Step size   Lf = sum over (k, r) in H of sum_{j<k, i} g_ji^2, g that row's adjoint coefficients above: the
+ *               squared Frobenius norm of u -> (row values), an upper bound of its Lipschitz constant.  Not finite
+ *               or not > 0: no candidate.
+ *   Iteration   FISTA, no restart, no line search.  u = clip(0, lb, ub), y = u, t = 1; for it = 1 .. max_iter:
+ *               x forward from x0 with the inputs y; v = max(C x - h, 0) on H; backwards P <- P + C_k' v_k,
+ *               g_j = B_j' P, P <- A_j' P; u+ = clip(y - g (1 / Lf), lb, ub); t+ = (1 + sqrt(1 + 4 t^2)) / 2;
+ *               y = u+ + ((t - 1) / t+)(u+ - u).
+ *   Check       when it % check_every == 0 and at it == max_iter: w = max(C x(u) - h, 0) on H at u (not y).
+ *               max w == 0: u satisfies every hard row; stop, no certificate, margin 0 (NaN data: stop, margin NaN).
+ *               Else w <- w / max w and the aggregated adjoint P_N = C_N' w_N, P_j = C_j' w_j + A_j' P_{j+1}
+ *               (1 <= j < N), P_0 = A_0' P_1, g_j = B_j' P_{j+1} gives
+ *                 reach = P_0'x0 + sum min(g_ji lb_i, g_ji ub_i)   (g_ji == 0 counts 0)
+ *                 S     = sum |w h| + sum_s |P_0s x0_s| + sum |g_ji| |the minimising bound|,   d = reach - w'h
+ *               and the agent is certified, and the iteration stops, when d > CMPC_CERT_TOL * S.  An input with an
+ *               infinite bound that the aggregate touches (g_ji != 0 with an infinite minimising bound) disqualifies
+ *               the check (NaN margin).
+ * The check is the single-row test on the aggregated row, rigorous whatever the iteration has or has not converged
+ * to.  The ray, in the layout of cmpc_mpc_duals.y: w on the stage rows; t = -g_ji split by sign onto input i's two
+ * box rows of stage j, as above; nu_j = -P_j on the state rows; 0 on the slack and input-rate rows.
+ *
+ * The certificate is sufficient, not necessary, and is for infeasibility by a margin: the iterations needed grow
+ * roughly as 1 / gap (on the test shapes a planted gap of 0.3 takes 8 .. 320 iterations, 0.01 up to about 1150, and
+ * 1e-4 is often not certified within 2000), so a barely infeasible agent keeps the solver's status.  Soft rows never
+ * count: a slack always satisfies them.
+ *
+ * cmpc_mpc_certify_rows_dev: DEVICE pointers, one launch, graph-capturable, one wavefront per agent; of dev_in it
+ * reads A, B, x0, C and h.  status (in-out, may be NULL: every agent is examined): an agent at CMPC_SOLVED,
+ * CMPC_SOLVED_INACCURATE or CMPC_PRIMAL_INFEASIBLE is skipped (none of its outputs is written); a certified agent's
+ * status becomes CMPC_PRIMAL_INFEASIBLE.  For an examined agent: margin = d / S of the last check, NaN without a
+ * candidate; iters = iterations done; nrows = rows with w > 0 at the last check; the ray row as above when
+ * certified, else all NaN.  max_iter <= 0 / check_every <= 0 select CMPC_CERT_ROWS_MAX_ITER /
+ * CMPC_CERT_ROWS_CHECK_EVERY.  cmpc_mpc_certify_rows: the same with HOST pointers (outputs copied in and out).
+ * Argument checks as cmpc_mpc_certify; CMPC_ERR_UNSUPPORTED when the iterates of the horizon do not fit LDS
+ * (8 (2 nu + mc) N bytes > 160 KB).  batch == 0: CMPC_OK without a launch. */
+#define CMPC_CERT_ROWS_MAX_ITER 512
+#define CMPC_CERT_ROWS_CHECK_EVERY 8
+typedef struct {
+    double* ray;     /* batch x ny, may be NULL */
+    double* margin;  /* batch, may be NULL */
+    int* iters;      /* batch, may be NULL */
+    int* nrows;      /* batch, may be NULL */
+} cmpc_mpc_cert_rows;
+
+int cmpc_mpc_certify_rows(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                          const cmpc_mpc_data* host_in, int* status, const cmpc_mpc_cert_rows* host_cert,
+                          int max_iter, int check_every);
+int cmpc_mpc_certify_rows_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                              const cmpc_mpc_data* dev_in, int* status, const cmpc_mpc_cert_rows* dev_cert,
+                              int max_iter, int check_every, void* hip_stream);
 
 /* The solver a structured batch would run, and how many of its workgroups share a CU — host only
  * (no context, no device).  Every solver uses more than 256 VGPRs + AGPRs per lane, so one
