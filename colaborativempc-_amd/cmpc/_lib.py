@@ -52,6 +52,18 @@ CMPC_CERT_TOL = 1e-9       # the certificate's threshold on (reach - h) / S
 CMPC_FLAG_CERTIFY_ROWS = 8192   # with CERTIFY: then the combined-row certificate on the agents still short of 1, 2, -3
 CMPC_CERT_ROWS_MAX_ITER = 512   # the combined-row certificate's iteration cap ...
 CMPC_CERT_ROWS_CHECK_EVERY = 8  # ... and the iterations between two of its reachability checks
+CMPC_FLAG_LPV = 16384       # the caller's promise: every agent holds the reference structure (structure.lpv_level >= 1)
+CMPC_FLAG_LPV_AUTO = 32768  # host entries: the detector decides after the upload (cmpc_mpc_lpv_level_dev)
+
+
+def lpv_flags(lpv):
+    """The flag bits of a wrapper's ``lpv`` argument: False: none; True: CMPC_FLAG_LPV (the caller's promise);
+    "auto": CMPC_FLAG_LPV_AUTO (host-pointer entries: the library runs the detector first)."""
+    if isinstance(lpv, str):
+        if lpv != "auto":
+            raise ValueError(f"lpv: True, False or 'auto', not {lpv!r}")
+        return CMPC_FLAG_LPV_AUTO
+    return CMPC_FLAG_LPV if lpv else 0
 
 
 def certify_flags(certify):
@@ -256,6 +268,10 @@ SIGNATURES = {
     "cmpc_mpc_certify_rows_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
                                              ct.POINTER(cmpc_mpc_data), _IP, ct.POINTER(cmpc_mpc_cert_rows),
                                              ct.c_int, ct.c_int, ct.c_void_p]),
+    "cmpc_mpc_lpv_level": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                      ct.POINTER(cmpc_mpc_data), _IP, _IP]),
+    "cmpc_mpc_lpv_level_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                          ct.POINTER(cmpc_mpc_data), _IP, _IP, ct.c_void_p]),
     "cmpc_solve_lpv_batch": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lpv_params), ct.POINTER(cmpc_track),
                                         ct.POINTER(cmpc_lpv_dims), ct.POINTER(cmpc_lpv_data),
                                         ct.POINTER(cmpc_lpv_out), ct.POINTER(cmpc_opts)]),

@@ -128,7 +128,8 @@ def _dua_res(x, y, P, q, G, A):
     return float(np.abs(np.asarray(r).ravel()).max(initial=0.0))
 
 
-def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True, certify_rows=False):
+def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True, certify_rows=False,
+                        lpv_structure=False):
     """Many ``osqp_solve_qp`` calls in as few GPU launches as possible: ``qps`` is a list of
     (P, q, G, h, A, b) tuples.  Every QP that ``structure.recognize`` identifies as a
     reference-form agent QP (LPV_Planner.py:156-157) joins one structured batch per distinct
@@ -139,7 +140,10 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True,
     feasible = 0 and the Farkas ray in ``res.prim_inf_cert`` (length m + m_eq, OSQP order); every other
     result has ``prim_inf_cert = None`` (the dense path's -3 carries no ray).  ``certify_rows``: the combined-row
     certificate as well (CMPC_FLAG_CERTIFY_ROWS, cmpc.infeas.certify_rows: hard rows that are each reachable alone
-    but contradict each other), with its ray in ``res.prim_inf_cert``; off, the adapter is what it is without it."""
+    but contradict each other), with its ray in ``res.prim_inf_cert``; off, the adapter is what it is without it.
+    ``lpv_structure``: the structured launch runs with ``solve_mpc(lpv="auto")``: the detector checks the uploaded
+    batch, and where every agent holds the reference structure (every QP the reference itself builds) the condensed
+    kernel's compact instantiation solves it; off (the default), the adapter's iterates are what they were."""
     from . import structure as St
     from .infeas import certify_gpu, certify_rows_gpu
     from .solver import PER_AGENT, solve_mpc
@@ -159,7 +163,8 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True,
         # CMPC_FLAG_CERTIFY: OSQP's -3 ("primal infeasible", feasible = 0) for an agent with a verified Farkas
         # ray; res.prim_inf_cert (OSQP order [G rows; A rows]) from one certificate launch on those agents
         z, kkt, it, st, y, dua = solve_mpc(batch, ctx, tol=tol, max_iter=max_iter, rescue=True, polish=True,
-                                           duals=True, certify="rows" if certify_rows else True)
+                                           duals=True, certify="rows" if certify_rows else True,
+                                           lpv="auto" if lpv_structure else False)
         rays = {}
         bad = np.nonzero(st == L.CMPC_PRIMAL_INFEASIBLE)[0]
         if bad.size:
@@ -196,7 +201,8 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True,
     return out
 
 
-def osqp_solve_qp(P, q, G=None, h=None, A=None, b=None, initvals=None, ctx=None, certify_rows=False):
+def osqp_solve_qp(P, q, G=None, h=None, A=None, b=None, initvals=None, ctx=None, certify_rows=False,
+                  lpv_structure=False):
     """Drop-in for the reference's ``osqp_solve_qp`` (LPV_Planner.py:192-249): the same QP
     (min 1/2 x'Px + q'x s.t. G x <= h, A x = b) solved on the GPU, returning (res, feasible)
     with ``res.x``, ``res.info.status_val`` / ``.status`` (OSQP codes), ``.obj_val``, ``.iter``,
@@ -205,5 +211,6 @@ def osqp_solve_qp(P, q, G=None, h=None, A=None, b=None, initvals=None, ctx=None,
     QP and solved by the structured kernels, "dense" otherwise).  ``initvals`` is accepted
     but unused: the reference passes it to ``osqp.warm_start`` (:237-238), while the
     interior-point method here starts from its own interior point (the caller in the
-    reference, PlannerLPV.solve :156-157, never passes it).  ``certify_rows``: as ``osqp_solve_qp_batch``."""
-    return osqp_solve_qp_batch([(P, q, G, h, A, b)], ctx=ctx, certify_rows=certify_rows)[0]
+    reference, PlannerLPV.solve :156-157, never passes it).  ``certify_rows``, ``lpv_structure``: as ``osqp_solve_qp_batch``."""
+    return osqp_solve_qp_batch([(P, q, G, h, A, b)], ctx=ctx, certify_rows=certify_rows,
+                               lpv_structure=lpv_structure)[0]

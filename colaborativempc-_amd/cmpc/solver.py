@@ -51,11 +51,12 @@ def check_shapes(p, batch):
 FP32_TOL = 1e-6   # default tolerance of the fp32 path (BASELINE cfg5; lane kernel, mixed precision)
 
 
-def _flags(fp32=False, riccati=False, generic=False, rescue=False, lane=False, polish=False, certify=False):
+def _flags(fp32=False, riccati=False, generic=False, rescue=False, lane=False, polish=False, certify=False,
+           lpv=False):
     return (L.CMPC_FLAG_FP32 if fp32 else 0) | (L.CMPC_FLAG_RICCATI if riccati else 0) | \
         (L.CMPC_FLAG_GENERIC if generic else 0) | (L.CMPC_FLAG_RESCUE if rescue else 0) | \
         (L.CMPC_FLAG_LANE if lane else 0) | (L.CMPC_FLAG_POLISH if polish else 0) | \
-        L.certify_flags(certify)
+        L.certify_flags(certify) | L.lpv_flags(lpv)
 
 
 def plan(shared, batch=1, fp32=False, riccati=False, generic=False, lane=False, rescue=False, polish=False, flags=0):
@@ -79,7 +80,7 @@ def plan(shared, batch=1, fp32=False, riccati=False, generic=False, lane=False, 
 
 
 def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, generic=False, rescue=False,
-              stamps=None, lane=False, polish=False, duals=False, certify=False, flags=0):
+              stamps=None, lane=False, polish=False, duals=False, certify=False, flags=0, lpv=False):
     """Solve a batch of structured agent-QPs on the GPU (host arrays in/out).
     ``fp32``: the fp32 path (BASELINE cfg5): fp32 Riccati factorisation and Newton recursions with
     fp64 iterates — the Riccati kernel's fp32 mode where it is instantiated (nx, nu, mc = 6, 3, 6),
@@ -101,6 +102,11 @@ def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, g
     Farkas ray (cmpc.infeas: single-row reachability) gets status CMPC_PRIMAL_INFEASIBLE (-3); z, kkt, iters and
     every other status are bit-identical to the call without it; ``certify="rows"``: CMPC_FLAG_CERTIFY_ROWS as
     well: then the combined-row certificate (cmpc.infeas.certify_rows) on the agents still short of 1, 2 and -3;
+    ``lpv``: True: CMPC_FLAG_LPV, the caller's promise that every agent holds the reference structure
+    (cmpc.structure.lpv_level >= 1): an eligible batch runs the condensed kernel's compact instantiation (the one
+    PlannerLPVBatch.solve runs), any other ignores it; the promise is not checked, and entries outside the pattern are
+    then not read.  "auto": CMPC_FLAG_LPV_AUTO, the library runs the detector on the uploaded batch and behaves as
+    True when every agent conforms, as False otherwise;
     ``flags``: further CMPC_FLAG_* bits.
 
     Returns (z (B,nz), kkt (B,), iters (B,), status (B,)), with ``duals`` (z, kkt, iters, status, y, dua_res)."""
@@ -116,7 +122,7 @@ def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, g
     status = np.zeros(batch, np.int32)
     out = L.cmpc_mpc_out(L.dptr(z), L.dptr(kkt), L.iptr(iters), L.iptr(status))
     o = L.opts(tol or (FP32_TOL if fp32 else None), max_iter,
-               _flags(fp32, riccati, generic, rescue, lane, polish, certify) | int(flags), stamps)
+               _flags(fp32, riccati, generic, rescue, lane, polish, certify, lpv) | int(flags), stamps)
     if duals:
         from .duals import ny_of
 
@@ -148,13 +154,16 @@ def _tptr(t):
 
 
 def solve_mpc_dev(shared, dev, out, ctx=None, tol=None, max_iter=None, stream=None, fp32=False, riccati=False,
-                  lane=False, certify=False):
+                  lane=False, certify=False, lpv=False, flags=0):
     """Device-resident batch solve.  ``shared``: dict with dims + shared weights (host);
     ``dev``: dict of CUDA float64 tensors (PER_AGENT keys); ``out``: dict with
     'z' (float64) and optional 'kkt' (float64), 'iters', 'status' (int32) tensors; with a 'y' tensor
     (float64, B x cmpc.duals.ny_of) and optionally 'dua_res' (float64, B) the dual solution is written too
     (cmpc_solve_mpc_batch_duals_dev, one more launch on the same stream).  ``certify``: CMPC_FLAG_CERTIFY (needs
     out['status']; one more launch); ``"rows"``: CMPC_FLAG_CERTIFY_ROWS as well (one more).
+    ``lpv``: True: CMPC_FLAG_LPV (the caller's promise of the reference structure, as ``solve_mpc``; decide it with
+    cmpc.structure.lpv_level_gpu on the device arrays).  "auto" is the host entries' (it needs a host wait): the
+    library refuses it here (CmpcError, CMPC_ERR_ARG).  ``flags``: further CMPC_FLAG_* bits.
     Launches asynchronously on ``stream`` (default: torch's current stream)."""
     import torch
 
@@ -164,7 +173,7 @@ def solve_mpc_dev(shared, dev, out, ctx=None, tol=None, max_iter=None, stream=No
     data = L.cmpc_mpc_data(*[_tptr(dev[k]) for k in PER_AGENT])
     o_ = L.cmpc_mpc_out(_tptr(out["z"]), _tptr(out.get("kkt")), _tptr(out.get("iters")), _tptr(out.get("status")))
     s = stream if stream is not None else torch.cuda.current_stream(dev["A"].device)
-    o = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, _flags(fp32, riccati, lane=lane, certify=certify))
+    o = L.opts(tol or (FP32_TOL if fp32 else None), max_iter, _flags(fp32, riccati, lane=lane, certify=certify, lpv=lpv) | int(flags))
     if out.get("y") is not None:
         du = L.cmpc_mpc_duals(_tptr(out["y"]), _tptr(out.get("dua_res")))
         ctx.check(ctx.lib.cmpc_solve_mpc_batch_duals_dev(ctx.h, ct.byref(_dims(shared, batch)), ct.byref(w),

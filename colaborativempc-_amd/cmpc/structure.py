@@ -432,3 +432,74 @@ def stack(probs):
     for k in ("A", "B", "x0", "u_prev", "qlin", "C", "h"):
         out[k] = np.concatenate([p[k] for p in probs])
     return out
+
+
+# ---- the reference structure of a structured batch (include/cmpc.h, cmpc_mpc_lpv_level) ----
+_LPV_ROW_SLACK = (-1, 0, 1, 1, 2, 2, 2)
+_LPV_ROW_SIGN = (1, 1, 1, 1, -1, -1, -1)
+
+
+def lpv_eligible(p):
+    """0 when the batch dict ``p`` is not eligible for the condensed kernel's compact instantiation (cmpc.h: nx, nu,
+    ns = 9, 2, 3, mc = 4 + nb with nb <= 3, N <= 32, N nu <= 64, the v3 row tables, Q diagonal), else the level of
+    its conforming agents: 2 when Q is zero on states 1, 2, 5, 6, else 1.  No flag is considered."""
+    nx, nu, N, ns, mc = (int(p[k]) for k in ("nx", "nu", "N", "ns", "mc"))
+    if (nx, nu, ns) != (9, 2, 3) or not 4 <= mc <= 7 or N < 1 or N > 32 or N * nu > 64:
+        return 0
+    sl = np.asarray(p["row_slack"]).ravel()
+    sg = np.where(np.asarray(p["row_sign"]).ravel() >= 0, 1, -1)   # the library's normalisation
+    if sl.size != mc or sg.size != mc or tuple(int(v) for v in sl) != _LPV_ROW_SLACK[:mc] or \
+            tuple(int(v) for v in sg) != _LPV_ROW_SIGN[:mc]:
+        return 0
+    Q = np.asarray(p["Q"], float).reshape(9, 9)
+    if ((Q != 0.0) & ~np.eye(9, dtype=bool)).any():
+        return 0
+    return 2 if all(Q[i, i] == 0.0 for i in (1, 2, 5, 6)) else 1
+
+
+def lpv_conforms(p):
+    """Per agent of the batch dict ``p`` ((B,) bool; nx = 9, nu = 2, mc >= 4): at every stage A_k is the identity
+    outside columns 0..2, B_k is zero outside rows 0..2, and the rows' coefficients are zero outside column 0
+    (rows 0, 1), column 3 (rows 2, 3) and columns 7, 8 (rows 4..) - the entries the compact load of the v3 kernel
+    never reads.  By value: -0.0 conforms, NaN does not.  Whatever the horizon: eligibility is lpv_eligible's."""
+    A, Bm, C = (np.asarray(p[k], float) for k in ("A", "B", "C"))
+    bad = (A[:, :, :, 3:] != np.eye(9)[:, 3:]).any(axis=(1, 2, 3))
+    bad |= (Bm[:, :, 3:, :] != 0.0).any(axis=(1, 2, 3))
+    read = np.zeros((C.shape[2], 9), bool)
+    read[0:2, 0] = True
+    read[2:4, 3] = True
+    read[4:, 7:9] = True
+    bad |= ((C != 0.0) & ~read).any(axis=(1, 2, 3))
+    return ~bad
+
+
+def lpv_level(p):
+    """The numpy statement of cmpc_mpc_lpv_level: per agent of the batch dict ``p`` (int32, (B,)) 0 when the batch is
+    not eligible (lpv_eligible) or the agent does not conform (lpv_conforms), else 1, or 2 when Q is also zero on
+    states 1, 2, 5, 6."""
+    batch = np.shape(p["A"])[0]
+    q = lpv_eligible(p)
+    if not q:
+        return np.zeros(batch, np.int32)
+    return np.where(lpv_conforms(p), q, 0).astype(np.int32)
+
+
+def lpv_level_gpu(p, ctx=None, count=False):
+    """cmpc_mpc_lpv_level on the batch dict ``p`` (host arrays): the detector kernel's levels, (B,) int32; with
+    ``count`` also the number of agents at level 0, as the kernel counted it."""
+    import ctypes as ct
+
+    from . import _lib as L
+    from .solver import _dims, _weights
+
+    ctx = ctx or L.default_context()
+    batch = int(np.shape(p["A"])[0])
+    w, keep = _weights(p)
+    arrs = [L.f64(p[k]) for k in ("A", "B", "C")]
+    data = L.cmpc_mpc_data(L.dptr(arrs[0]), L.dptr(arrs[1]), None, None, None, L.dptr(arrs[2]), None)
+    level = np.full(batch, -1, np.int32)
+    non = np.full(1, -1, np.int32)
+    ctx.check(ctx.lib.cmpc_mpc_lpv_level(ctx.h, ct.byref(_dims(p, batch)), ct.byref(w), ct.byref(data),
+                                         L.iptr(level), L.iptr(non)))
+    del keep, arrs
+    return (level, int(non[0])) if count else level

@@ -233,6 +233,9 @@ static int solve_mpc_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mp
     const char* msg = nullptr;
     int rc = cmpc::mpc_prepare(dims, w, opts, &c, &msg);
     if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (opts && (opts->flags & CMPC_FLAG_LPV_AUTO) && !(opts->flags & CMPC_FLAG_LPV))
+        return fail(ctx, CMPC_ERR_ARG, "CMPC_FLAG_LPV_AUTO needs a host wait, so a device-pointer entry cannot take it: "
+                                       "run cmpc_mpc_lpv_level_dev and pass CMPC_FLAG_LPV");
     if (du && (rc = want_duals(ctx, &c)) != CMPC_OK) return rc;
     if ((rc = set_device(ctx)) != CMPC_OK) return rc;
     if (du && dims->batch == 0) return CMPC_OK;
@@ -425,6 +428,64 @@ int cmpc_mpc_certify_rows(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
     return CMPC_OK;
 }
 
+int cmpc_mpc_lpv_level_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                           int* level, int* nonconforming, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!dims || !w || !in || (!level && !nonconforming)) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::MpcConst c;
+    const char* msg = nullptr;
+    int rc = cmpc::mpc_prepare(dims, w, nullptr, &c, &msg);
+    if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (!in->A || !in->B || (c.mc && !in->C)) return fail(ctx, CMPC_ERR_ARG, "null data");
+    if (dims->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int q = cmpc::mpc_lpv_eligible(c, 0);
+    if (!q) {  // not eligible: every level 0, no launch
+        if (level) HIP_TRY(hipMemsetAsync(level, 0, 4 * (size_t)dims->batch, s));
+        if (nonconforming) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)nonconforming, dims->batch, 1, s));
+        return CMPC_OK;
+    }
+    HIP_TRY(cmpc::mpc_lpv_detect_launch(c, q, in->A, in->B, in->C, level, nonconforming, dims->batch, s));
+    return CMPC_OK;
+}
+
+int cmpc_mpc_lpv_level(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                       int* level, int* nonconforming) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!d || !w || !in || (!level && !nonconforming)) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::MpcConst c;
+    const char* msg = nullptr;
+    int rc = cmpc::mpc_prepare(d, w, nullptr, &c, &msg);
+    if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (!in->A || !in->B || (c.mc && !in->C)) return fail(ctx, CMPC_ERR_ARG, "null data");
+    if (d->batch == 0) return CMPC_OK;
+    const int q = cmpc::mpc_lpv_eligible(c, 0);
+    if (!q) {  // not eligible: nothing is uploaded or launched
+        if (level) std::memset(level, 0, 4 * (size_t)d->batch);
+        if (nonconforming) *nonconforming = d->batch;
+        return CMPC_OK;
+    }
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    const size_t B = d->batch, N = d->N, mc = d->mc;
+    const size_t sA = B * N * 81, sB = B * N * 18, sC = B * N * mc * 9;
+    char* base = arena(ctx, 8 * (sA + sB + sC) + 4 * (B + 1) + 5 * 256);
+    if (!base) return fail(ctx, CMPC_ERR_NOMEM, "device arena allocation failed");
+    Carve cv{base};
+    double *dA = cv.take<double>(sA), *dB = cv.take<double>(sB), *dC = cv.take<double>(sC);
+    int *dl = cv.take<int>(B), *dn = cv.take<int>(1);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dA, in->A, 8 * sA, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dB, in->B, 8 * sB, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dC, in->C, 8 * sC, hipMemcpyHostToDevice, s));
+    HIP_TRY(cmpc::mpc_lpv_detect_launch(c, q, dA, dB, dC, level ? dl : nullptr, nonconforming ? dn : nullptr, d->batch,
+                                        s));
+    if (level) HIP_TRY(hipMemcpyAsync(level, dl, 4 * B, hipMemcpyDeviceToHost, s));
+    if (nonconforming) HIP_TRY(hipMemcpyAsync(nonconforming, dn, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
 int cmpc_plan_mpc(const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_opts* opts, cmpc_plan_info* out) {
     if (!dims || !w || !out) return CMPC_ERR_ARG;
     cmpc::MpcConst c;
@@ -471,8 +532,11 @@ static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
                  sC = B * N * mc * nx, sh = B * N * mc, sz = B * mpc_nz(*d);
     const size_t sw = cmpc::mpc_ws_doubles(c) * B;
     const size_t sy = dl ? B * ((size_t)c.m + (size_t)(d->nx + d->ns) * (N + 1) + nu * N) : 0;
+    // CMPC_FLAG_LPV_AUTO: the detector decides after the upload (0 here: not eligible, or CMPC_FLAG_LPV has decided)
+    const int flags = opts ? opts->flags : 0;
+    const int auto_level = ((flags & CMPC_FLAG_LPV_AUTO) && !(flags & CMPC_FLAG_LPV) && B) ? cmpc::mpc_lpv_eligible(c, flags) : 0;
     const size_t bytes = 8 * (sA + sB + sx + su + sp + sC + sh + sz + B + sw + sy + (dl ? B : 0)) + 8 * B +
-                         4 * (B + 1) + 16 * 256 + (dl ? 2 * 256 : 0);
+                         4 * (B + 1) + 16 * 256 + (dl ? 2 * 256 : 0) + (auto_level ? 256 + 4 : 0);
     char* base = arena(ctx, bytes);
     if (!base) return fail(ctx, CMPC_ERR_NOMEM, "device arena allocation failed");
     Carve cv{base};
@@ -483,6 +547,7 @@ static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
     double* dw = sw ? cv.take<double>(sw) : nullptr;
     int* dpl = sw ? cv.take<int>(B + 1) : nullptr;  // the polish launch's compacted agent list
     double *dy = dl ? cv.take<double>(sy) : nullptr, *dr = dl ? cv.take<double>(B) : nullptr;
+    int* dnc = auto_level ? cv.take<int>(1) : nullptr;
     hipStream_t s = ctx->stream;
     HIP_TRY(hipMemcpyAsync(dA, in->A, 8 * sA, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dB, in->B, 8 * sB, hipMemcpyHostToDevice, s));
@@ -491,6 +556,14 @@ static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
     HIP_TRY(hipMemcpyAsync(dp, in->qlin, 8 * sp, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dC, in->C, 8 * sC, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dh, in->h, 8 * sh, hipMemcpyHostToDevice, s));
+    if (auto_level) {
+        // one launch on the device copies, 4 bytes back, one stream wait (this entry synchronises anyway)
+        int nonconforming = 0;
+        HIP_TRY(cmpc::mpc_lpv_detect_launch(c, auto_level, dA, dB, dC, nullptr, dnc, d->batch, s));
+        HIP_TRY(hipMemcpyAsync(&nonconforming, dnc, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nonconforming == 0) c.lpv = auto_level;
+    }
     cmpc::MpcPtrs p{dA, dB, dx0, du, dp, dC, dh, dz, dk, di, ds,
                     opts ? (unsigned long long*)opts->stamps : nullptr, dw};  // stamps: device memory
     p.plist = dpl;
@@ -769,7 +842,9 @@ static int di_solve(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims
     cmpc::DiPtrs dp{nbr, lane, traj_all, const_cast<double*>(in->qlin), const_cast<double*>(in->C),
                     const_cast<double*>(in->h)};
     HIP_TRY(cmpc::di_build_launch(dc, dp, dd->batch, s));
-    rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream);
+    cmpc_opts plain = opts ? *opts : cmpc_opts{};
+    plain.flags &= ~CMPC_FLAG_LPV_AUTO;  // (the fused round ignores both structure flags)
+    rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts ? &plain : nullptr, stream);
     if (rc != CMPC_OK || !traj_local) return rc;
     HIP_TRY(cmpc::di_advance_launch(dc, out->z, const_cast<double*>(in->x0), const_cast<double*>(in->u_prev),
                                     traj_local, dd->batch, s));

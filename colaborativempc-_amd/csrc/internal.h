@@ -25,7 +25,8 @@ struct MpcConst {
     int riccati;  // 1: stage-wise Riccati kernel (fp64, N*nu > 64 or CMPC_FLAG_RICCATI)
     int rescue;   // 1: CMPC_FLAG_RESCUE on a condensed solve (Riccati re-solve of broken-down agents); 2: its
                   // cold second pass; 3: the fp32 path's fp64 pass over the agents short of tol (mpc_launch)
-    int lpv;      // 1: data made by lpv_build.hip with Q diagonal (the v3 kernel's LS layout applies); 2: and Q zero
+    int lpv;      // 1: data made by lpv_build.hip, or promised to hold its structure (CMPC_FLAG_LPV on an eligible batch,
+                  // mpc_lpv_eligible), with Q diagonal (the v3 kernel's LS layout applies); 2: and Q zero
                   // on states 1, 2, 5, 6 (the LS kernel's L5 contraction, the reference's config_LPV.py:7)
     int finish;   // 1: CMPC_FLAG_FINISH (rescue also continues breakdowns at the rounding floor)
     int lane;     // lane-per-agent kernel (mpc_lane.hip): 1 fp64 (CMPC_FLAG_LANE), 2 mixed fp32 (CMPC_FLAG_FP32 | LANE,
@@ -225,6 +226,13 @@ bool mpc3_try_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t
 // LDS bytes of the v3 instantiation mpc3_try_launch would run for c (0: none covers it)
 size_t mpc3_lds_bytes(const MpcConst& c);
 size_t mpc_lane_lds_bytes(const MpcConst& c);
+// Reference structure (mpc_lpv_detect.hip; cmpc.h, cmpc_mpc_lpv_level).  mpc_lpv_eligible: 0 when the batch is not
+// eligible under `flags`, else the level of its conforming agents (1, or 2: Q zero on states 1, 2, 5, 6) — the value
+// of MpcConst::lpv that CMPC_FLAG_LPV selects.  The detector: level[b] (may be null) <- qlevel or 0, *noncon (may
+// be null; zeroed on the stream first) += agents at 0; reads A, B, C of an eligible batch only
+int mpc_lpv_eligible(const MpcConst& c, int flags);
+hipError_t mpc_lpv_detect_launch(const MpcConst& c, int qlevel, const double* A, const double* B, const double* C,
+                                 int* level, int* noncon, int batch, hipStream_t s);
 // Dual solution in OSQP's form (mpc_dual.hip): y (batch x (m + ne (N + 1) + nu N)) and dua_res (batch, may be
 // null) from z and agent b's multipliers at lam + b * lam_stride; valid (may be null): agent b's marker at
 // valid + b * valid_stride, anything but 1.0 gives NaN outputs.  Reads A, B, p, C, h of `p` only

@@ -811,6 +811,9 @@ int mpc_prepare(const cmpc_mpc_dims* d, const cmpc_mpc_weights* wt, const cmpc_o
         c->row_slack[r] = wt->row_slack[r];
         c->row_sign[r] = wt->row_sign[r] >= 0 ? 1 : -1;
     }
+    // CMPC_FLAG_LPV: the caller's promise of the reference structure; on an eligible batch the v3 kernel's compact
+    // (LS) instantiation, anywhere else ignored.  (CMPC_FLAG_LPV_AUTO is the host entries' own: cmpc_api.hip)
+    c->lpv = (o && (o->flags & CMPC_FLAG_LPV)) ? mpc_lpv_eligible(*c, o->flags) : 0;
     return CMPC_OK;
 }
 

@@ -51,7 +51,8 @@ extern "C" {
                                 cmpc_lpv_rounds_log_* / cmpc_di_rounds_log_*, CMPC_LOG_SEPARATION;
                                 cmpc_mpc_duals, cmpc_solve_mpc_batch_duals[_dev], cmpc_mpc_duals_dev;
                                 CMPC_FLAG_CERTIFY, cmpc_mpc_cert, cmpc_mpc_certify[_dev];
-                                CMPC_FLAG_CERTIFY_ROWS, cmpc_mpc_cert_rows, cmpc_mpc_certify_rows[_dev] */
+                                CMPC_FLAG_CERTIFY_ROWS, cmpc_mpc_cert_rows, cmpc_mpc_certify_rows[_dev];
+                                CMPC_FLAG_LPV, CMPC_FLAG_LPV_AUTO, cmpc_mpc_lpv_level[_dev] */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -137,9 +138,26 @@ typedef struct cmpc_ctx cmpc_ctx;
                                        every agent and the status of every uncertified agent are bit-identical to
                                        the call without the flag.  A horizon whose iterates do not fit the
                                        certificate's LDS (cmpc_mpc_certify_rows) keeps the single-row statuses */
+#define CMPC_FLAG_LPV 16384 /* the caller's promise that every agent of the batch conforms to the reference structure
+                                (cmpc_mpc_lpv_level below: level 1 or 2).  On an eligible batch the specialised
+                                condensed kernel then runs its compact instantiation (the one cmpc_solve_lpv_batch
+                                runs: about half the LDS image, cmpc_plan_mpc reports it); on any other batch the flag
+                                is ignored.  The library never checks the promise against device memory: a batch that
+                                breaks it is solved as if every entry outside the pattern held the pattern's value
+                                (memory-safe: the compact loads stay inside the same arrays).  Everything behind the
+                                solve (rescue, polish, duals, both certificates) reads the caller's arrays as before.
+                                Honoured by cmpc_solve_mpc_batch[_dev] and cmpc_solve_mpc_batch_duals[_dev]; ignored by
+                                the round handles and the fused double-integrator round */
+#define CMPC_FLAG_LPV_AUTO 32768 /* HOST-pointer entries only (cmpc_solve_mpc_batch, cmpc_solve_mpc_batch_duals): after
+                                    the upload the detector (cmpc_mpc_lpv_level_dev) runs on the device copies and the
+                                    library reads its nonconforming count back (4 bytes, one stream wait); the call
+                                    then behaves as with CMPC_FLAG_LPV when the count is 0 and as with neither flag
+                                    otherwise.  On cmpc_solve_mpc_batch_dev / _duals_dev: CMPC_ERR_ARG (it would need a
+                                    host wait and could not be captured).  With CMPC_FLAG_LPV as well: CMPC_FLAG_LPV.
+                                    Ignored where CMPC_FLAG_LPV is */
 #define CMPC_FLAG_ALL (CMPC_FLAG_GENERIC | CMPC_FLAG_FP32 | CMPC_FLAG_RICCATI | CMPC_FLAG_RESCUE | CMPC_FLAG_FINISH | \
                        CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES | CMPC_FLAG_LTI | \
-                       CMPC_FLAG_CERTIFY | CMPC_FLAG_CERTIFY_ROWS)
+                       CMPC_FLAG_CERTIFY | CMPC_FLAG_CERTIFY_ROWS | CMPC_FLAG_LPV | CMPC_FLAG_LPV_AUTO)
                        /* other bits: CMPC_ERR_ARG */
 
 typedef struct {
@@ -373,6 +391,35 @@ int cmpc_mpc_certify_rows(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_m
 int cmpc_mpc_certify_rows_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                               const cmpc_mpc_data* dev_in, int* status, const cmpc_mpc_cert_rows* dev_cert,
                               int max_iter, int check_every, void* hip_stream);
+
+/* Reference structure of a structured batch: the pattern of the reference's own agent QPs (LPV_Planner.py:493-585,
+ * :279-380) under which the specialised condensed kernel keeps compact images (CMPC_FLAG_LPV).  This is the one
+ * definition; cmpc.structure.lpv_level is its numpy statement, and the entries it constrains are exactly those the
+ * compact (LS) load of mpc_ipm3.hip never reads (checked against that code: D_k = A_k - I on columns 0..2, B_k rows
+ * 0..2, the rows' coefficients on vx / ey / (X, Y)).
+ *
+ * A batch is eligible when nx = 9, nu = 2, ns = 3, mc = 4 + nb with 0 <= nb <= 3, N <= 32 and N nu <= 64; row_slack is
+ * {-1, 0, 1, 1, 2, ...} and row_sign {+1, +1, +1, +1, -1, ...} (a sign >= 0 counts as +1, as everywhere in the library);
+ * Q has no nonzero off-diagonal entry; and none of CMPC_FLAG_GENERIC, RICCATI, LANE, FP32 is set.
+ * Agent b of an eligible batch conforms when at every stage k, comparing by value (x != 0.0: -0.0 conforms, NaN does
+ * not; denormals are not flushed):
+ *   A[b,k,r,t] == (r == t ? 1 : 0) for every column t >= 3;   B[b,k,r,:] == 0 for every row r >= 3;
+ *   C[b,k,0..1,:] is zero outside column 0, C[b,k,2..3,:] outside column 3, C[b,k,4+j,:] outside columns 7, 8.
+ * Level of an agent: 0 when the batch is not eligible or the agent does not conform; else 2 when Q[1,1], Q[2,2], Q[5,5]
+ * and Q[6,6] are all 0.0 (the kernel's further contraction, the reference's config_LPV.py:7), else 1.
+ *
+ * cmpc_mpc_lpv_level_dev: DEVICE pointers, stream-ordered, graph-capturable, no scratch: one launch (a workgroup per
+ * agent streams that agent's A, B and C once) writes level[b] (may be NULL) and, after the library has zeroed it on the
+ * stream, adds the number of agents at level 0 to *nonconforming (may be NULL; a device int).  A batch that is not
+ * eligible gets level 0 everywhere and *nonconforming = batch without a launch (the entry takes no
+ * options, so eligibility is judged with no flag set).
+ * cmpc_mpc_lpv_level: the same with HOST pointers (upload, one launch, copy back; synchronises).
+ * CMPC_ERR_ARG: NULL dims, w, in, in->A, in->B, NULL in->C when mc > 0, or level and nonconforming both NULL; dimension
+ * errors as cmpc_solve_mpc_batch.  batch == 0: CMPC_OK without a launch. */
+int cmpc_mpc_lpv_level_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                           const cmpc_mpc_data* dev_in, int* level, int* nonconforming, void* hip_stream);
+int cmpc_mpc_lpv_level(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                       const cmpc_mpc_data* host_in, int* level, int* nonconforming);
 
 /* The solver a structured batch would run, and how many of its workgroups share a CU — host only
  * (no context, no device).  Every solver uses more than 256 VGPRs + AGPRs per lane, so one
