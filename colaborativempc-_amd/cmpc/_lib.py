@@ -54,14 +54,19 @@ CMPC_CERT_ROWS_MAX_ITER = 512   # the combined-row certificate's iteration cap .
 CMPC_CERT_ROWS_CHECK_EVERY = 8  # ... and the iterations between two of its reachability checks
 CMPC_FLAG_LPV = 16384       # the caller's promise: every agent holds the reference structure (structure.lpv_level >= 1)
 CMPC_FLAG_LPV_AUTO = 32768  # host entries: the detector decides after the upload (cmpc_mpc_lpv_level_dev)
+CMPC_FLAG_LPV_SPLIT = 65536  # every entry: the detector and a partition route each agent to its kernel on the device
 
 
 def lpv_flags(lpv):
     """The flag bits of a wrapper's ``lpv`` argument: False: none; True: CMPC_FLAG_LPV (the caller's promise);
-    "auto": CMPC_FLAG_LPV_AUTO (host-pointer entries: the library runs the detector first)."""
+    "auto": CMPC_FLAG_LPV_AUTO (host-pointer entries: the library runs the detector first); "split":
+    CMPC_FLAG_LPV_SPLIT (host and device entries: each agent goes to its kernel on the device, nothing is read
+    back)."""
     if isinstance(lpv, str):
+        if lpv == "split":
+            return CMPC_FLAG_LPV_SPLIT
         if lpv != "auto":
-            raise ValueError(f"lpv: True, False or 'auto', not {lpv!r}")
+            raise ValueError(f"lpv: True, False, 'auto' or 'split', not {lpv!r}")
         return CMPC_FLAG_LPV_AUTO
     return CMPC_FLAG_LPV if lpv else 0
 
@@ -272,6 +277,7 @@ SIGNATURES = {
                                       ct.POINTER(cmpc_mpc_data), _IP, _IP]),
     "cmpc_mpc_lpv_level_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
                                           ct.POINTER(cmpc_mpc_data), _IP, _IP, ct.c_void_p]),
+    "cmpc_mpc_lpv_split_dev": (ct.c_int, [ct.c_void_p, ct.c_int, _IP, _IP, _IP, ct.c_void_p]),
     "cmpc_solve_lpv_batch": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lpv_params), ct.POINTER(cmpc_track),
                                         ct.POINTER(cmpc_lpv_dims), ct.POINTER(cmpc_lpv_data),
                                         ct.POINTER(cmpc_lpv_out), ct.POINTER(cmpc_opts)]),

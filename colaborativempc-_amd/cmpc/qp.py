@@ -143,7 +143,9 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True,
     but contradict each other), with its ray in ``res.prim_inf_cert``; off, the adapter is what it is without it.
     ``lpv_structure``: the structured launch runs with ``solve_mpc(lpv="auto")``: the detector checks the uploaded
     batch, and where every agent holds the reference structure (every QP the reference itself builds) the condensed
-    kernel's compact instantiation solves it; off (the default), the adapter's iterates are what they were."""
+    kernel's compact instantiation solves it; ``"split"``: ``solve_mpc(lpv="split")``, each agent goes to its kernel
+    on the device, so one QP off the pattern no longer costs the others the compact kernel; off (the default), the
+    adapter's iterates are what they were."""
     from . import structure as St
     from .infeas import certify_gpu, certify_rows_gpu
     from .solver import PER_AGENT, solve_mpc
@@ -164,7 +166,8 @@ def osqp_solve_qp_batch(qps, ctx=None, tol=None, max_iter=None, structured=True,
         # ray; res.prim_inf_cert (OSQP order [G rows; A rows]) from one certificate launch on those agents
         z, kkt, it, st, y, dua = solve_mpc(batch, ctx, tol=tol, max_iter=max_iter, rescue=True, polish=True,
                                            duals=True, certify="rows" if certify_rows else True,
-                                           lpv="auto" if lpv_structure else False)
+                                           lpv=lpv_structure if isinstance(lpv_structure, str) else
+                                           ("auto" if lpv_structure else False))
         rays = {}
         bad = np.nonzero(st == L.CMPC_PRIMAL_INFEASIBLE)[0]
         if bad.size:

@@ -106,7 +106,9 @@ def solve_mpc(p, ctx=None, tol=None, max_iter=None, fp32=False, riccati=False, g
     (cmpc.structure.lpv_level >= 1): an eligible batch runs the condensed kernel's compact instantiation (the one
     PlannerLPVBatch.solve runs), any other ignores it; the promise is not checked, and entries outside the pattern are
     then not read.  "auto": CMPC_FLAG_LPV_AUTO, the library runs the detector on the uploaded batch and behaves as
-    True when every agent conforms, as False otherwise;
+    True when every agent conforms, as False otherwise.  "split": CMPC_FLAG_LPV_SPLIT, the detector and a partition
+    run on the device and each agent goes to its kernel: a conforming agent's outputs are bit-identical to the
+    call with True, any other agent's to the call with False;
     ``flags``: further CMPC_FLAG_* bits.
 
     Returns (z (B,nz), kkt (B,), iters (B,), status (B,)), with ``duals`` (z, kkt, iters, status, y, dua_res)."""
@@ -163,7 +165,8 @@ def solve_mpc_dev(shared, dev, out, ctx=None, tol=None, max_iter=None, stream=No
     out['status']; one more launch); ``"rows"``: CMPC_FLAG_CERTIFY_ROWS as well (one more).
     ``lpv``: True: CMPC_FLAG_LPV (the caller's promise of the reference structure, as ``solve_mpc``; decide it with
     cmpc.structure.lpv_level_gpu on the device arrays).  "auto" is the host entries' (it needs a host wait): the
-    library refuses it here (CmpcError, CMPC_ERR_ARG).  ``flags``: further CMPC_FLAG_* bits.
+    library refuses it here (CmpcError, CMPC_ERR_ARG).  "split": CMPC_FLAG_LPV_SPLIT, as ``solve_mpc``: decided per agent
+    on the device on every call, stream-ordered, nothing read back.  ``flags``: further CMPC_FLAG_* bits.
     Launches asynchronously on ``stream`` (default: torch's current stream)."""
     import torch
 

@@ -503,3 +503,43 @@ def lpv_level_gpu(p, ctx=None, count=False):
                                          L.iptr(level), L.iptr(non)))
     del keep, arrs
     return (level, int(non[0])) if count else level
+
+
+def lpv_split(level):
+    """The numpy statement of cmpc_mpc_lpv_split_dev: (conf, rest), int32 arrays of length batch + 1.  conf[:nc] holds
+    the agents with level > 0 in ascending order and conf[batch] = nc; rest[:nr] the others in ascending order and
+    rest[batch] = nr.  The entries the kernel leaves untouched are -1 here, for comparison only."""
+    level = np.asarray(level).ravel()
+    batch = level.size
+    on = level > 0
+    conf = np.full(batch + 1, -1, np.int32)
+    rest = np.full(batch + 1, -1, np.int32)
+    ic, ir = np.nonzero(on)[0], np.nonzero(~on)[0]
+    conf[:ic.size] = ic
+    rest[:ir.size] = ir
+    conf[batch] = ic.size
+    rest[batch] = ir.size
+    return conf, rest
+
+
+def lpv_split_gpu(level, ctx=None, fill=-1):
+    """cmpc_mpc_lpv_split_dev on ``level`` (a host array, uploaded): (conf, rest) as the kernel left them, int32
+    arrays of length batch + 1 that held ``fill`` everywhere before the launch."""
+    import ctypes as ct
+
+    import torch
+
+    from . import _lib as L
+    from .solver import _tptr
+
+    ctx = ctx or L.default_context()
+    dev = torch.device("cuda", ctx.device)
+    lv = torch.as_tensor(np.ascontiguousarray(level, np.int32).ravel(), device=dev)
+    batch = int(lv.numel())
+    conf = torch.full((batch + 1,), int(fill), dtype=torch.int32, device=dev)
+    rest = torch.full((batch + 1,), int(fill), dtype=torch.int32, device=dev)
+    s = torch.cuda.current_stream(dev)
+    ctx.check(ctx.lib.cmpc_mpc_lpv_split_dev(ctx.h, batch, _tptr(lv) if batch else None, _tptr(conf), _tptr(rest),
+                                             ct.c_void_p(s.cuda_stream)))
+    s.synchronize()
+    return conf.cpu().numpy(), rest.cpu().numpy()

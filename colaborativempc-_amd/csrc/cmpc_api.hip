@@ -240,18 +240,25 @@ static int solve_mpc_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mp
     if ((rc = set_device(ctx)) != CMPC_OK) return rc;
     if (du && dims->batch == 0) return CMPC_OK;
     double* ws = nullptr;
-    int* plist = nullptr;
-    if (const size_t wsd = cmpc::mpc_ws_doubles(c) * (size_t)dims->batch) {
+    int *plist = nullptr, *split = nullptr;
+    const size_t wsd = cmpc::mpc_ws_doubles(c) * (size_t)dims->batch;
+    // CMPC_FLAG_LPV_SPLIT: level, conf and rest (3 batch + 2 ints), also where the solve itself needs no scratch
+    const size_t nsplit = cmpc::mpc_lpv_split_level(c, opts ? opts->flags : 0, dims->batch) ? 3 * (size_t)dims->batch + 2 : 0;
+    if (wsd || nsplit) {
         // (+ the polish launch's compacted agent list: batch + 1 ints after the scratch)
-        ws = reinterpret_cast<double*>(arena(ctx, 8 * wsd + 4 * ((size_t)dims->batch + 1)));
-        if (!ws) return fail(ctx, CMPC_ERR_NOMEM, "device scratch allocation failed");
-        plist = reinterpret_cast<int*>(ws + wsd);
+        char* base = arena(ctx, 8 * wsd + 4 * ((size_t)dims->batch + 1 + nsplit));
+        if (!base) return fail(ctx, CMPC_ERR_NOMEM, "device scratch allocation failed");
+        if (wsd) {
+            ws = reinterpret_cast<double*>(base);
+            plist = reinterpret_cast<int*>(ws + wsd);
+        }
+        if (nsplit) split = reinterpret_cast<int*>(base + 8 * wsd) + dims->batch + 1;
     }
     cmpc::MpcPtrs p{in->A, in->B, in->x0, in->u_prev, in->qlin, in->C, in->h, out->z, out->kkt, out->iters, out->status,
                     opts ? (unsigned long long*)opts->stamps : nullptr, ws};
     p.order = opts ? opts->order : nullptr;
     p.plist = plist;
-    HIP_TRY(cmpc::mpc_launch(c, p, dims->batch, (hipStream_t)stream, opts ? opts->flags : 0));
+    HIP_TRY(cmpc::mpc_launch(c, p, dims->batch, (hipStream_t)stream, opts ? opts->flags : 0, split));
     if (du) HIP_TRY(duals_after(c, p, du, dims->batch, (hipStream_t)stream));
     return CMPC_OK;
 }
@@ -486,6 +493,22 @@ int cmpc_mpc_lpv_level(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_wei
     return CMPC_OK;
 }
 
+int cmpc_mpc_lpv_split_dev(cmpc_ctx* ctx, int batch, const int* level, int* conf, int* rest, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (batch < 0) return fail(ctx, CMPC_ERR_ARG, "negative batch");
+    if (batch == 0) return CMPC_OK;
+    if (!level || !conf || !rest) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    // level over batch ints, conf and rest over batch + 1
+    const auto overlap = [](const int* a, size_t na, const int* b, size_t nb) { return a < b + nb && b < a + na; };
+    const size_t nl = (size_t)batch, no = (size_t)batch + 1;
+    if (overlap(level, nl, conf, no) || overlap(level, nl, rest, no) || overlap(conf, no, rest, no))
+        return fail(ctx, CMPC_ERR_ARG, "level, conf and rest must not alias each other");
+    int rc = set_device(ctx);
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(cmpc::mpc_lpv_split_launch(batch, level, conf, rest, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
 int cmpc_plan_mpc(const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_opts* opts, cmpc_plan_info* out) {
     if (!dims || !w || !out) return CMPC_ERR_ARG;
     cmpc::MpcConst c;
@@ -534,9 +557,13 @@ static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
     const size_t sy = dl ? B * ((size_t)c.m + (size_t)(d->nx + d->ns) * (N + 1) + nu * N) : 0;
     // CMPC_FLAG_LPV_AUTO: the detector decides after the upload (0 here: not eligible, or CMPC_FLAG_LPV has decided)
     const int flags = opts ? opts->flags : 0;
-    const int auto_level = ((flags & CMPC_FLAG_LPV_AUTO) && !(flags & CMPC_FLAG_LPV) && B) ? cmpc::mpc_lpv_eligible(c, flags) : 0;
+    // CMPC_FLAG_LPV_SPLIT: decided per agent on the device (mpc_launch), and it decides where both are set
+    const bool split = cmpc::mpc_lpv_split_level(c, flags, d->batch) != 0;
+    const int auto_level = ((flags & CMPC_FLAG_LPV_AUTO) && !(flags & CMPC_FLAG_LPV) && !split && B)
+                               ? cmpc::mpc_lpv_eligible(c, flags) : 0;
     const size_t bytes = 8 * (sA + sB + sx + su + sp + sC + sh + sz + B + sw + sy + (dl ? B : 0)) + 8 * B +
-                         4 * (B + 1) + 16 * 256 + (dl ? 2 * 256 : 0) + (auto_level ? 256 + 4 : 0);
+                         4 * (B + 1) + 16 * 256 + (dl ? 2 * 256 : 0) + (auto_level ? 256 + 4 : 0) +
+                         (split ? 256 + 4 * (3 * B + 2) : 0);
     char* base = arena(ctx, bytes);
     if (!base) return fail(ctx, CMPC_ERR_NOMEM, "device arena allocation failed");
     Carve cv{base};
@@ -548,6 +575,7 @@ static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
     int* dpl = sw ? cv.take<int>(B + 1) : nullptr;  // the polish launch's compacted agent list
     double *dy = dl ? cv.take<double>(sy) : nullptr, *dr = dl ? cv.take<double>(B) : nullptr;
     int* dnc = auto_level ? cv.take<int>(1) : nullptr;
+    int* dsp = split ? cv.take<int>(3 * B + 2) : nullptr;  // level, conf, rest
     hipStream_t s = ctx->stream;
     HIP_TRY(hipMemcpyAsync(dA, in->A, 8 * sA, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dB, in->B, 8 * sB, hipMemcpyHostToDevice, s));
@@ -567,7 +595,7 @@ static int solve_mpc_host(cmpc_ctx* ctx, const cmpc_mpc_dims* d, const cmpc_mpc_
     cmpc::MpcPtrs p{dA, dB, dx0, du, dp, dC, dh, dz, dk, di, ds,
                     opts ? (unsigned long long*)opts->stamps : nullptr, dw};  // stamps: device memory
     p.plist = dpl;
-    HIP_TRY(cmpc::mpc_launch(c, p, d->batch, s, opts ? opts->flags : 0));
+    HIP_TRY(cmpc::mpc_launch(c, p, d->batch, s, opts ? opts->flags : 0, dsp));
     if (dl) {
         const cmpc_mpc_duals dd{dy, dr};
         HIP_TRY(duals_after(c, p, &dd, d->batch, s));
@@ -843,7 +871,7 @@ static int di_solve(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_dims
                     const_cast<double*>(in->h)};
     HIP_TRY(cmpc::di_build_launch(dc, dp, dd->batch, s));
     cmpc_opts plain = opts ? *opts : cmpc_opts{};
-    plain.flags &= ~CMPC_FLAG_LPV_AUTO;  // (the fused round ignores both structure flags)
+    plain.flags &= ~(CMPC_FLAG_LPV_AUTO | CMPC_FLAG_LPV_SPLIT);  // (the fused round ignores the structure flags)
     rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts ? &plain : nullptr, stream);
     if (rc != CMPC_OK || !traj_local) return rc;
     HIP_TRY(cmpc::di_advance_launch(dc, out->z, const_cast<double*>(in->x0), const_cast<double*>(in->u_prev),

@@ -99,6 +99,9 @@ struct MpcPtrs {
     // optional device scratch of batch + 1 ints for the polish launch's compacted agent list (mpc_polish.hip):
     // without it every workgroup maps to its own agent and the flagged ones queue behind each other on a CU
     int* plist = nullptr;
+    // optional agent list of a v3 launch (mpc_ipm3.hip; CMPC_FLAG_LPV_SPLIT), the same convention: workgroup i solves
+    // agent alist[i], and a workgroup at or beyond the count alist[gridDim.x] returns at once; null: its own agent
+    const int* alist = nullptr;
 };
 
 // Interior-point safeguards shared by both solver kernels and the C oracle (oracle/cmpc_oracle.c).
@@ -219,8 +222,14 @@ inline size_t mpc_ws_doubles(const MpcConst& c) {
 int mpc_prepare(const cmpc_mpc_dims* d, const cmpc_mpc_weights* w, const cmpc_opts* o,
                 MpcConst* c, const char** msg);
 size_t mpc_lds_bytes(const MpcConst& c);
-// flags: CMPC_FLAG_GENERIC forces the generic kernel (diagnostics)
-hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, int flags = 0);
+// flags: CMPC_FLAG_GENERIC forces the generic kernel (diagnostics).  split: device scratch of 3 batch + 2 ints (the
+// detector's level, then the two agent lists of batch + 1 each), needed exactly when mpc_lpv_split_level(c, flags,
+// batch) is not 0 (hipErrorInvalidValue without it)
+hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, int flags = 0, int* split = nullptr);
+// CMPC_FLAG_LPV_SPLIT applies to this solve: the flag on an eligible batch (mpc_lpv_eligible) without the promise
+// (c.lpv, as mpc_prepare or the caller set it).  0, or the level its conforming agents run at.  The one predicate:
+// the entries size the scratch by it and mpc_launch acts on it
+int mpc_lpv_split_level(const MpcConst& c, int flags, int batch);
 // v3 kernels of mpc_ipm3.hip (PlannerLPV row pattern, N <= 32); false when none covers the problem.
 bool mpc3_try_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, hipError_t* err);
 // LDS bytes of the v3 instantiation mpc3_try_launch would run for c (0: none covers it)
@@ -233,6 +242,10 @@ size_t mpc_lane_lds_bytes(const MpcConst& c);
 int mpc_lpv_eligible(const MpcConst& c, int flags);
 hipError_t mpc_lpv_detect_launch(const MpcConst& c, int qlevel, const double* A, const double* B, const double* C,
                                  int* level, int* noncon, int batch, hipStream_t s);
+// The stable partition by level (mpc_lpv_split.hip; cmpc.h, cmpc_mpc_lpv_split_dev): conf / rest (batch + 1 ints each)
+// <- the agents with level > 0 / the others, ascending, the counts at index batch.  One workgroup; nothing is
+// launched for batch <= 0
+hipError_t mpc_lpv_split_launch(int batch, const int* level, int* conf, int* rest, hipStream_t s);
 // Dual solution in OSQP's form (mpc_dual.hip): y (batch x (m + ne (N + 1) + nu N)) and dua_res (batch, may be
 // null) from z and agent b's multipliers at lam + b * lam_stride; valid (may be null): agent b's marker at
 // valid + b * valid_stride, anything but 1.0 gives NaN outputs.  Reads A, B, p, C, h of `p` only

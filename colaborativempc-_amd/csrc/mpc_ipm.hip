@@ -827,11 +827,16 @@ static hipError_t launch_t(const MpcConst& c, const MpcPtrs& p, int batch, hipSt
     return hipGetLastError();
 }
 
-static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags);
+static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags,
+                                 int* split);
 
-hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, int flags) {
+int mpc_lpv_split_level(const MpcConst& c, int flags, int batch) {
+    return ((flags & CMPC_FLAG_LPV_SPLIT) && !c.lpv && batch > 0) ? mpc_lpv_eligible(c, flags) : 0;
+}
+
+hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_t s, int flags, int* split) {
     if (batch == 0) return hipSuccess;
-    const hipError_t e = solve_launches(c, p, batch, s, flags);
+    const hipError_t e = solve_launches(c, p, batch, s, flags, split);
     // certificate (CMPC_FLAG_CERTIFY) last, behind every solver path: it reads the problem data and the final
     // statuses only; the fused double-integrator round keeps its rows in LDS only, so it has none to certify
     // against (as the polish below)
@@ -843,7 +848,8 @@ hipError_t mpc_launch(const MpcConst& c, const MpcPtrs& p, int batch, hipStream_
     return mpc_infeas_rows_launch(c, p, p.status, nullptr, nullptr, nullptr, nullptr, 0, 0, batch, s);
 }
 
-static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags) {
+static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int batch, hipStream_t s, int flags,
+                                 int* split) {
     MpcConst c = c_in;
     c.ws_stride = p.ws ? mpc_ws_doubles(c) : 0;
     if (c.duals && (!p.ws || c.lane || c.f32)) return hipErrorInvalidValue;
@@ -862,7 +868,26 @@ static hipError_t solve_launches(const MpcConst& c_in, const MpcPtrs& p, int bat
         return mpc_riccati_launch(c64, p, batch, s);
     }
     hipError_t e;
-    if (flags & CMPC_FLAG_GENERIC || !mpc3_try_launch(c, p, batch, s, &e)) {
+    // CMPC_FLAG_LPV_SPLIT on an eligible batch without the promise (mpc_lpv_split_level; the fused round's
+    // dimensions are never eligible): the detector, the partition, then the compact instantiation on the conforming
+    // agents and the general one on the others.  Both with one workgroup per agent of the batch (the counts stay on
+    // the device): a workgroup beyond its list's count returns at once, and every agent is in exactly one list
+    const int qsplit = p.fuse.on ? 0 : mpc_lpv_split_level(c, flags, batch);
+    if (qsplit) {
+        if (!split) return hipErrorInvalidValue;
+        int *level = split, *conf = level + batch, *rest = conf + batch + 1;
+        if ((e = mpc_lpv_detect_launch(c, qsplit, p.A, p.B, p.C, level, nullptr, batch, s)) != hipSuccess) return e;
+        if ((e = mpc_lpv_split_launch(batch, level, conf, rest, s)) != hipSuccess) return e;
+        MpcConst cc = c;
+        cc.lpv = qsplit;
+        MpcPtrs pc = p, pr = p;
+        pc.alist = conf;
+        pr.alist = rest;
+        // (an eligible batch is one the v3 kernel covers; the generic kernel takes no list)
+        if (!mpc3_try_launch(cc, pc, batch, s, &e)) return hipErrorInvalidValue;
+        if (e != hipSuccess) return e;
+        if (!mpc3_try_launch(c, pr, batch, s, &e)) return hipErrorInvalidValue;
+    } else if (flags & CMPC_FLAG_GENERIC || !mpc3_try_launch(c, p, batch, s, &e)) {
         switch (c.npad / 16) {
             case 1: e = launch_t<1>(c, p, batch, s); break;
             case 2: e = launch_t<2>(c, p, batch, s); break;

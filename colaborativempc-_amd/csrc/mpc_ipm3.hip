@@ -600,7 +600,17 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
     extern __shared__ __attribute__((aligned(16))) double sm[];
     static_assert(!W2 || DS, "W2: the fused double-integrator instantiation");
     static_assert(!TI || (DS && !W2), "TI: the one-wave fused double-integrator instantiation");
-    const int l0 = threadIdx.x & 63, b = blockIdx.x, N = c.N, n = N * NU, ms = N * MC;
+    int b = blockIdx.x;
+    // with an agent list (MpcPtrs::alist, CMPC_FLAG_LPV_SPLIT): workgroup i solves the list's i-th agent, and the
+    // workgroups beyond its count have none.  Wave-uniform: scalar loads and a scalar branch.  Everything below is
+    // indexed by the agent.  The fused double-integrator instantiations never take a list
+    if constexpr (!DS) {
+        if (P.alist) {
+            if (b >= P.alist[gridDim.x]) return;
+            b = P.alist[b];
+        }
+    }
+    const int l0 = threadIdx.x & 63, N = c.N, n = N * NU, ms = N * MC;
     const int l = l0;
     // the wave index as a scalar (wave-uniform: the branches on it are scalar, never exec-masked)
     const int wvi = W2 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;

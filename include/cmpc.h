@@ -52,7 +52,8 @@ extern "C" {
                                 cmpc_mpc_duals, cmpc_solve_mpc_batch_duals[_dev], cmpc_mpc_duals_dev;
                                 CMPC_FLAG_CERTIFY, cmpc_mpc_cert, cmpc_mpc_certify[_dev];
                                 CMPC_FLAG_CERTIFY_ROWS, cmpc_mpc_cert_rows, cmpc_mpc_certify_rows[_dev];
-                                CMPC_FLAG_LPV, CMPC_FLAG_LPV_AUTO, cmpc_mpc_lpv_level[_dev] */
+                                CMPC_FLAG_LPV, CMPC_FLAG_LPV_AUTO, cmpc_mpc_lpv_level[_dev];
+                                CMPC_FLAG_LPV_SPLIT, cmpc_mpc_lpv_split_dev */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -155,9 +156,29 @@ typedef struct cmpc_ctx cmpc_ctx;
                                     otherwise.  On cmpc_solve_mpc_batch_dev / _duals_dev: CMPC_ERR_ARG (it would need a
                                     host wait and could not be captured).  With CMPC_FLAG_LPV as well: CMPC_FLAG_LPV.
                                     Ignored where CMPC_FLAG_LPV is */
+#define CMPC_FLAG_LPV_SPLIT 65536 /* the per-agent form of CMPC_FLAG_LPV_AUTO, decided on the device on every call: on an
+                                     eligible batch (cmpc_mpc_lpv_level below) the single condensed launch becomes four
+                                     on the same stream: the detector into a per-agent level, the partition
+                                     (cmpc_mpc_lpv_split_dev below), the compact instantiation on the conforming agents
+                                     and the general one on the others (both with one workgroup per agent of the batch:
+                                     a workgroup beyond its list's count returns at once).  Nothing comes back to the
+                                     host and nothing is promised: an agent off the pattern is solved from all of its
+                                     data.  Rescue, polish, duals and both certificates follow unchanged on the whole
+                                     batch.  Guarantee: per agent, z, kkt, iters, status (and y, dua_res of the duals
+                                     entries) are bit-identical to a reference call on the same batch and options: for a
+                                     conforming agent the call with CMPC_FLAG_LPV, for any other agent the call with no
+                                     structure flag.  Scratch: 3 batch + 2 ints of the context's arena.  Honoured by
+                                     cmpc_solve_mpc_batch[_dev] and cmpc_solve_mpc_batch_duals[_dev] (stream-ordered
+                                     on the device entries: no host wait).  With CMPC_FLAG_LPV as well the promise wins
+                                     (no detection); with CMPC_FLAG_LPV_AUTO on a host entry this flag decides (on a
+                                     device entry CMPC_FLAG_LPV_AUTO stays CMPC_ERR_ARG).  Ignored on a batch that is
+                                     not eligible and wherever CMPC_FLAG_LPV is ignored.  cmpc_plan_mpc accepts it and
+                                     reports what it reports without it: the general image, the worst case over the
+                                     two launches */
 #define CMPC_FLAG_ALL (CMPC_FLAG_GENERIC | CMPC_FLAG_FP32 | CMPC_FLAG_RICCATI | CMPC_FLAG_RESCUE | CMPC_FLAG_FINISH | \
                        CMPC_FLAG_LANE | CMPC_FLAG_POLISH | CMPC_FLAG_ONE_WAVE | CMPC_FLAG_TWO_WAVES | CMPC_FLAG_LTI | \
-                       CMPC_FLAG_CERTIFY | CMPC_FLAG_CERTIFY_ROWS | CMPC_FLAG_LPV | CMPC_FLAG_LPV_AUTO)
+                       CMPC_FLAG_CERTIFY | CMPC_FLAG_CERTIFY_ROWS | CMPC_FLAG_LPV | CMPC_FLAG_LPV_AUTO | \
+                       CMPC_FLAG_LPV_SPLIT)
                        /* other bits: CMPC_ERR_ARG */
 
 typedef struct {
@@ -420,6 +441,16 @@ int cmpc_mpc_lpv_level_dev(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_
                            const cmpc_mpc_data* dev_in, int* level, int* nonconforming, void* hip_stream);
 int cmpc_mpc_lpv_level(cmpc_ctx* ctx, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                        const cmpc_mpc_data* host_in, int* level, int* nonconforming);
+
+/* The stable partition of a batch by the detector's level (the second launch of CMPC_FLAG_LPV_SPLIT).  DEVICE
+ * pointers, one launch (one 1024-thread workgroup, 1024 agents per step), stream-ordered, no host wait, no scratch.
+ * conf[0 .. nc) <- the agents with level[b] > 0 in ascending order and conf[batch] <- nc; rest[0 .. nr) <- the others
+ * in ascending order and rest[batch] <- nr; nc + nr = batch.  The result is fully determined by level.  conf and rest
+ * hold batch + 1 ints each; the entries conf[nc .. batch) and rest[nr .. batch) are left untouched.
+ * cmpc.structure.lpv_split is its numpy statement.
+ * batch == 0: CMPC_OK without a launch.  CMPC_ERR_ARG: batch < 0; a NULL pointer with batch > 0; level, conf and rest
+ * overlapping each other (level over batch ints, conf and rest over batch + 1). */
+int cmpc_mpc_lpv_split_dev(cmpc_ctx* ctx, int batch, const int* level, int* conf, int* rest, void* hip_stream);
 
 /* The solver a structured batch would run, and how many of its workgroups share a CU — host only
  * (no context, no device).  Every solver uses more than 256 VGPRs + AGPRs per lane, so one
