@@ -180,7 +180,7 @@ class cmpc_lpv_rounds_out(ct.Structure):
     _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("planes", _DP)]
 
 
-CMPC_ROUNDS_LPT = 8        # cmpc_di_rounds: launch order = cmpc_order_by_iters_dev of the previous round's iterations
+CMPC_ROUNDS_LPT = 8        # cmpc_di_rounds / cmpc_lin_rounds: launch order = cmpc_order_by_iters_dev of the previous round's iterations
 
 
 class cmpc_di_rounds_dims(ct.Structure):
@@ -192,6 +192,32 @@ class cmpc_di_rounds_init(ct.Structure):
 
 
 class cmpc_di_rounds_out(ct.Structure):
+    _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP)]
+
+
+class cmpc_lin_params(ct.Structure):   # position = state columns ix, iy
+    _fields_ = [("ix", ct.c_int), ("iy", ct.c_int), ("min_dist", ct.c_double), ("wq", ct.c_double)]
+
+
+class cmpc_lin_dims(ct.Structure):     # mo own rows per stage; mc = mo + nb
+    _fields_ = [(k, ct.c_int) for k in ("batch", "N", "nb", "self_offset", "nx", "mo")]
+
+
+class cmpc_lin_own(ct.Structure):      # device pointers
+    _fields_ = [("qlin_own", _DP), ("C_own", _DP), ("h_own", _DP)]
+
+
+class cmpc_lin_rounds_dims(ct.Structure):
+    _fields_ = [(k, ct.c_int) for k in ("n_total", "batch", "self_offset", "N", "nb", "flags", "history", "nx", "nu",
+                                        "ns", "mo")]
+
+
+class cmpc_lin_rounds_init(ct.Structure):
+    _fields_ = [("A", _DP), ("B", _DP), ("x0", _DP), ("u_prev", _DP), ("qlin_own", _DP), ("C_own", _DP),
+                ("h_own", _DP), ("nbr", _IP), ("traj", _DP)]
+
+
+class cmpc_lin_rounds_out(ct.Structure):
     _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP)]
 
 
@@ -344,6 +370,27 @@ SIGNATURES = {
     "cmpc_di_rounds_log_enable": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
     "cmpc_di_rounds_log_range": (ct.c_int, [ct.c_void_p, _IP, _IP]),
     "cmpc_di_rounds_log_read": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_rounds_log)]),
+    "cmpc_lin_build_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_lin_dims), _IP,
+                                      ct.POINTER(cmpc_lin_own), _DP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_lin_advance_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_lin_dims), ct.c_int,
+                                        ct.c_int, _DP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_lin_round_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_lin_dims), _IP,
+                                      ct.POINTER(cmpc_lin_own), _DP, ct.POINTER(cmpc_mpc_dims),
+                                      ct.POINTER(cmpc_mpc_weights), ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out),
+                                      ct.POINTER(cmpc_opts), _DP, ct.c_void_p]),
+    "cmpc_lin_rounds_create": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_mpc_weights),
+                                          ct.POINTER(cmpc_lin_rounds_dims), ct.POINTER(cmpc_lin_rounds_init),
+                                          ct.POINTER(cmpc_opts), ct.POINTER(ct.c_void_p)]),
+    "cmpc_lin_rounds_step": (ct.c_int, [ct.c_void_p, ct.c_int, _IP]),
+    "cmpc_lin_rounds_read": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_rounds_out)]),
+    "cmpc_lin_rounds_history": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _DP, _IP, _IP]),
+    "cmpc_lin_rounds_get_traj": (ct.c_int, [ct.c_void_p, _DP]),
+    "cmpc_lin_rounds_set_traj": (ct.c_int, [ct.c_void_p, _DP]),
+    "cmpc_lin_rounds_set_state": (ct.c_int, [ct.c_void_p, _DP, _DP]),
+    "cmpc_lin_rounds_destroy": (ct.c_int, [ct.c_void_p]),
+    "cmpc_lin_rounds_log_enable": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
+    "cmpc_lin_rounds_log_range": (ct.c_int, [ct.c_void_p, _IP, _IP]),
+    "cmpc_lin_rounds_log_read": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_rounds_log)]),
 }
 
 CMPC_COMM_ID_BYTES = 128

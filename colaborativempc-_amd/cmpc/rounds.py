@@ -160,6 +160,95 @@ def log_round_dev(z, nx, nu, ns, N, look_col, row=None, kkt=None, iters=None, st
     return row
 
 
+def _lin_params(prm):
+    """cmpc_lin_params of a ``prm`` dict(ix, iy, min_dist, wq)."""
+    return L.cmpc_lin_params(int(prm["ix"]), int(prm["iy"]), float(prm["min_dist"]), float(prm["wq"]))
+
+
+def _lin_args(traj_all, nbr, own, self_offset, ctx, stream):
+    """What the three linear-model wrappers share: the shapes read off the tensors, cmpc_lin_dims, cmpc_lin_own."""
+    import torch
+
+    q = own["qlin_own"]
+    B, N, nx = int(q.shape[0]), int(q.shape[1]) - 1, int(q.shape[2])
+    C_own, h_own = own.get("C_own"), own.get("h_own")
+    mo = 0 if C_own is None else int(C_own.shape[2])
+    nb = 0 if nbr is None else int(nbr.shape[1])
+    if traj_all.dim() != 3 or tuple(traj_all.shape[1:]) != (N + 1, 2) or (mo and tuple(h_own.shape) != (B, N, mo)):
+        raise ValueError("traj_all (n_total, N+1, 2), qlin_own (B, N+1, nx), C_own (B, N, mo, nx), h_own (B, N, mo)")
+    ctx = ctx or L.default_context(traj_all.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(traj_all.device)
+    dims = L.cmpc_lin_dims(B, N, nb, int(self_offset), nx, mo)
+    lo = L.cmpc_lin_own(_tptr(q), _tptr(C_own) if mo else None, _tptr(h_own) if mo else None)
+    return ctx, dims, lo, (_tptr(nbr) if nb and B else None), ct.c_void_p(getattr(stream, "cuda_stream", stream))
+
+
+def lin_build_dev(prm, own, nbr, traj_all, self_offset=0, out=None, ctx=None, stream=None):
+    """The linear-model family's builder on the device — one launch of cmpc_lin_build_dev on ``stream`` (default:
+    torch's current one), no host synchronisation; the rule is ``scenarios.lin_rows``'s, bit for bit.  ``prm``:
+    dict(ix, iy, min_dist, wq); ``own``: dict of contiguous fp64 CUDA tensors qlin_own (B, N+1, nx), C_own
+    (B, N, mo, nx), h_own (B, N, mo) (the last two None when mo = 0); ``nbr`` (B, nb) int32 (None when nb = 0);
+    ``traj_all`` (n_total, N+1, 2).  Writes ``out`` = (qlin, C, h) (allocated when None) and returns it."""
+    import torch
+
+    ctx, dims, lo, pn, st = _lin_args(traj_all, nbr, own, self_offset, ctx, stream)
+    B, N, nx, mc = dims.batch, dims.N, dims.nx, dims.mo + dims.nb
+    if out is None:
+        out = tuple(torch.empty(shp, dtype=torch.float64, device=traj_all.device)
+                    for shp in ((B, N + 1, nx), (B, N, mc, nx), (B, N, mc)))
+    qlin, C, h = out
+    if (tuple(qlin.shape), tuple(C.shape), tuple(h.shape)) != ((B, N + 1, nx), (B, N, mc, nx), (B, N, mc)):
+        raise ValueError("out: qlin (B, N+1, nx), C (B, N, mo+nb, nx), h (B, N, mo+nb)")
+    if B == 0 or mc == 0:   # empty tensors have no address to hand over; nothing to build beyond the copy of qlin
+        qlin.copy_(own["qlin_own"])
+        return out
+    ctx.check(ctx.lib.cmpc_lin_build_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(lo),
+                                         _tptr(traj_all), _tptr(qlin), _tptr(C), _tptr(h), st))
+    return out
+
+
+def lin_advance_dev(prm, z, nx, nu, ns, N, x0, u_prev, traj_local, ctx=None, stream=None):
+    """The family's advance on the device — one launch of cmpc_lin_advance_dev: ``x0`` (B, nx), ``u_prev`` (B, nu)
+    and ``traj_local`` (B, N+1, 2) are overwritten from ``z`` (B, nz, reference layout) for every agent whose z is
+    finite (``scenarios.lin_advance``); contiguous fp64 CUDA tensors."""
+    import torch
+
+    B = int(z.shape[0])
+    if z.dim() != 2 or z.shape[1] != (nx + ns) * (N + 1) + 2 * nu * N or tuple(x0.shape) != (B, nx) or \
+            tuple(u_prev.shape) != (B, nu) or tuple(traj_local.shape) != (B, N + 1, 2):
+        raise ValueError("z (B, (nx+ns)(N+1) + 2 nu N), x0 (B, nx), u_prev (B, nu), traj_local (B, N+1, 2)")
+    if B == 0:
+        return
+    ctx = ctx or L.default_context(z.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(z.device)
+    dims = L.cmpc_lin_dims(B, int(N), 0, 0, int(nx), 0)
+    ctx.check(ctx.lib.cmpc_lin_advance_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), int(ns), int(nu),
+                                           _tptr(z), _tptr(x0), _tptr(u_prev), _tptr(traj_local),
+                                           ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+
+
+def lin_round_dev(prm, own, nbr, traj_all, shared, dev, out, traj_local, self_offset=0, opts=None, ctx=None,
+                  stream=None):
+    """One round of the family on the device (cmpc_lin_round_dev): the builder into ``dev["qlin" | "C" | "h"]``,
+    cmpc_solve_mpc_batch_dev on ``dev`` (the PER_AGENT tensors of ``solver.solve_mpc_dev``) with ``shared`` (dims
+    and weights) and ``opts`` (a ``_lib.opts``; None: defaults), then the advance into ``dev["x0"]``,
+    ``dev["u_prev"]`` and ``traj_local``.  ``out``: dict with 'z' and optional 'kkt', 'iters', 'status'.  The
+    exchange traj_local -> traj_all stays the caller's."""
+    from .solver import PER_AGENT
+
+    ctx, dims, lo, pn, st = _lin_args(traj_all, nbr, own, self_offset, ctx, stream)
+    w, keep = _weights(shared)
+    data = L.cmpc_mpc_data(*[_tptr(dev[k]) for k in PER_AGENT])
+    o_ = L.cmpc_mpc_out(_tptr(out["z"]), _tptr(out.get("kkt")), _tptr(out.get("iters")), _tptr(out.get("status")))
+    ctx.check(ctx.lib.cmpc_lin_round_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(lo),
+                                         _tptr(traj_all), ct.byref(_dims(shared, dims.batch)), ct.byref(w),
+                                         ct.byref(data), ct.byref(o_), None if opts is None else ct.byref(opts),
+                                         _tptr(traj_local), st))
+    del keep
+
+
 def _di_params(p):
     """cmpc_di_params of a scenario's ``params``."""
     return L.cmpc_di_params(int(p["dim"]), *(float(p[k]) for k in ("v_ref", "q_v", "q_lane", "hw", "min_vel", "max_vel",
@@ -219,7 +308,7 @@ class _TorchRounds:
 
 
 class _RoundsHandle:
-    """What the two round-handle wrappers share (cmpc_lpv_rounds_* / cmpc_di_rounds_*, include/cmpc.h): the
+    """What the round-handle wrappers share (cmpc_lpv_rounds_* / cmpc_di_rounds_* / cmpc_lin_rounds_*): the
     handle's lifetime, the host exchange and the device log.  A wrapper sets ``_fn`` (the entry points' common
     prefix), ``ctx``, ``B``, ``n``, ``N`` and ``nx`` / ``nu`` (the widths of the log's state and input rows)."""
 
@@ -707,3 +796,87 @@ class DIRoundsHandle(_RoundsHandle):
                  status=np.zeros((max(count, 0), self.B), np.int32))
         self._call("history", int(first), count, L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]))
         return r
+
+
+class LinRoundsHandle(_RoundsHandle):
+    """Consensus rounds of agents with any linear model through the C ABI's round handle (cmpc_lin_rounds_*): the
+    library owns the device state; no torch.  ``shared``: dims and weights (nx, nu, N, ns, mc = mo + nb, Q, R, dR,
+    Qs, u_ub, u_lb, row_slack, row_sign); ``prm``: dict(ix, iy, min_dist, wq); ``own``: dict(qlin_own, C_own,
+    h_own) (``scenarios.lin_rows``); population arrays A (n, N, nx, nx), B (n, N, nx, nu), x0 (n, nx), u_prev
+    (n, nu), nbr (n, nb), own arrays with leading dimension n, traj (n, N+1, 2): this handle takes the contiguous
+    shard ``rank`` of ``world``.  ``opts``: a ``_lib.opts`` for the solver (None: defaults).  ``host_exchange``,
+    ``reselect``, ``lpt``, ``history``, ``log``, ``log_separation``: as ``DIRoundsHandle`` (``lpt`` None: its
+    default rule).  ``set_state`` replaces the predicted state by a measured one."""
+
+    _fn = "cmpc_lin_rounds_"
+
+    def __init__(self, shared, prm, own, A, B, x0, u_prev, nbr, traj, rank=0, world=1, ctx=None, opts=None,
+                 host_exchange=False, reselect=False, lpt=None, history=1, log=0, log_separation=False):
+        n = int(np.shape(x0)[0])
+        if n % world:
+            raise ValueError("agents must be divisible by the number of ranks")
+        self.ctx = ctx or L.default_context(0)
+        self.B, self.n, self.N = n // world, n, int(shared["N"])
+        sl = slice(rank * self.B, (rank + 1) * self.B)
+        nbr = L.i32(np.asarray(nbr).reshape(n, -1))
+        self.nb, self.nx, self.nu, self.ns = nbr.shape[1], int(shared["nx"]), int(shared["nu"]), int(shared["ns"])
+        self.mo = int(shared["mc"]) - self.nb
+        self.nz = nz_of(shared)
+        fp32 = bool(opts is not None and opts.flags & L.CMPC_FLAG_FP32)
+        self.lpt = _lpt_default(shared, self.N, fp32) if lpt is None else bool(lpt)
+        flags = self._flags(host_exchange, reselect=reselect, lpt=self.lpt)
+        self.dims = L.cmpc_lin_rounds_dims(n, self.B, sl.start, self.N, self.nb, flags, int(history), self.nx, self.nu,
+                                           self.ns, self.mo)
+        w, wkeep = _weights(shared)
+        opt = lambda a: None if a is None or self.mo == 0 else L.f64(np.asarray(a)[sl])   # noqa: E731
+        keep = [L.f64(np.asarray(A)[sl]), L.f64(np.asarray(B)[sl]), L.f64(np.asarray(x0)[sl]),
+                L.f64(np.asarray(u_prev)[sl]), L.f64(np.asarray(own["qlin_own"])[sl]), opt(own.get("C_own")),
+                opt(own.get("h_own")), L.i32(nbr[sl]), L.f64(traj)]
+        init = L.cmpc_lin_rounds_init(*[L.dptr(a) for a in keep[:7]], L.iptr(keep[7]) if self.nb else None,
+                                      L.dptr(keep[8]))
+        self._create((_lin_params(prm), w, self.dims, init, opts if opts is not None else L.opts()), log,
+                     log_separation)
+
+    @classmethod
+    def of_di(cls, scen, tol=None, max_iter=None, fp32=False, **kw):
+        """The handle of a ``scenarios.DIScenario`` expressed in this family (``scenarios.lin_of_di``): round for
+        round what ``DIRounds(scen, fused=False)`` computes."""
+        from .scenarios import lin_of_di
+
+        lin = lin_of_di(scen)
+        return cls(scen.shared, lin["prm"], lin["own"], scen.A, scen.B, scen.x0, scen.u_prev, scen.nbr, scen.traj,
+                   opts=_di_opts(tol, max_iter, fp32), **kw)
+
+    def step(self, rounds=1):
+        """Runs ``rounds`` rounds (one host synchronisation, at the end); returns the number done."""
+        done = ct.c_int()
+        self._call("step", int(rounds), ct.byref(done))
+        return done.value
+
+    def read(self):
+        """The latest round: dict of z, kkt, iters, status, x0, u_prev (the next round's), nbr."""
+        r = dict(z=np.zeros((self.B, self.nz)), kkt=np.zeros(self.B), iters=np.zeros(self.B, np.int32),
+                 status=np.zeros(self.B, np.int32), x0=np.zeros((self.B, self.nx)), u_prev=np.zeros((self.B, self.nu)),
+                 nbr=np.zeros((self.B, self.nb), np.int32))
+        o = L.cmpc_lin_rounds_out(L.dptr(r["z"]), L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]),
+                                  L.dptr(r["x0"]), L.dptr(r["u_prev"]), L.iptr(r["nbr"]) if self.nb else None)
+        self._call("read", ct.byref(o))
+        return r
+
+    def history(self, first, count):
+        """kkt, iters, status of rounds [first, first + count) (counted from create), each (count, B); a round
+        not yet run or already overwritten raises CmpcError(CMPC_ERR_ARG)."""
+        count = int(count)
+        r = dict(kkt=np.zeros((max(count, 0), self.B)), iters=np.zeros((max(count, 0), self.B), np.int32),
+                 status=np.zeros((max(count, 0), self.B), np.int32))
+        self._call("history", int(first), count, L.dptr(r["kkt"]), L.iptr(r["iters"]), L.iptr(r["status"]))
+        return r
+
+    def set_state(self, x0=None, u_prev=None):
+        """The next round solves from ``x0`` (B, nx) and ``u_prev`` (B, nu) instead of the predicted ones (None:
+        that part stays): the measured state of a real loop."""
+        a = None if x0 is None else L.f64(x0)
+        b = None if u_prev is None else L.f64(u_prev)
+        if (a is not None and a.shape != (self.B, self.nx)) or (b is not None and b.shape != (self.B, self.nu)):
+            raise ValueError("x0: (B, nx), u_prev: (B, nu)")
+        self._call("set_state", L.dptr(a), L.dptr(b))

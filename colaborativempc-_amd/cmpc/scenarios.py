@@ -151,6 +151,98 @@ def log_row(z, nx, nu, ns, N, look_col):
     return z[:, :nx].copy(), z[:, u0:u0 + nu].copy(), look
 
 
+def lin_rows(prm, own, nbr, traj, self_offset=0):
+    """Host statement of the linear-model family's builder (cmpc_lin_build_dev, include/cmpc.h), every expression
+    in the header's order, each numpy operation rounded once (no fma).  ``prm``: dict(ix, iy, min_dist, wq);
+    ``own``: dict(qlin_own (B, N+1, nx), C_own (B, N, mo, nx), h_own (B, N, mo)), C_own / h_own may be None when
+    the agents have no own rows; ``nbr`` (B, nb) global indices into ``traj`` (n_total, N+1, 2); the local agents
+    are rows self_offset .. self_offset + B of ``traj``.  Returns (qlin (B, N+1, nx), C (B, N, mo+nb, nx),
+    h (B, N, mo+nb)).  A neighbour on the agent's own point gives NaN rows and cost at that stage."""
+    ix, iy, d, wq = int(prm["ix"]), int(prm["iy"]), float(prm["min_dist"]), float(prm["wq"])
+    q_own = np.asarray(own["qlin_own"], np.float64)
+    B, N, nx = q_own.shape[0], q_own.shape[1] - 1, q_own.shape[2]
+    C_own = np.zeros((B, N, 0, nx)) if own.get("C_own") is None else np.asarray(own["C_own"], np.float64)
+    h_own = np.zeros((B, N, 0)) if own.get("h_own") is None else np.asarray(own["h_own"], np.float64)
+    mo = C_own.shape[2]
+    nbr = np.asarray(nbr, np.int64).reshape(B, -1)
+    nb = nbr.shape[1]
+    traj = np.asarray(traj, np.float64)
+    if not (0 <= ix < nx and 0 <= iy < nx and ix != iy) or C_own.shape != (B, N, mo, nx) or h_own.shape != (B, N, mo) \
+            or traj.shape[1:] != (N + 1, 2):
+        raise ValueError("lin_rows: ix != iy in [0, nx), C_own (B, N, mo, nx), h_own (B, N, mo), traj (n, N+1, 2)")
+    C = np.zeros((B, N, mo + nb, nx))
+    h = np.zeros((B, N, mo + nb))
+    C[:, :, :mo] = C_own
+    h[:, :, :mo] = h_own
+    me = traj[self_offset:self_offset + B]
+    px, py = np.zeros((B, N)), np.zeros((B, N))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i in range(nb):
+            nt = traj[nbr[:, i]]
+            ex, ey, nx_, ny_ = me[:, :-1, 0], me[:, :-1, 1], nt[:, :-1, 0], nt[:, :-1, 1]   # planes: row k-1
+            dx, dy = nx_ - ex, ny_ - ey
+            nrm = np.sqrt(dx * dx + dy * dy)
+            ax, ay = dx / nrm, dy / nrm
+            bb = -0.5 * (ax * (ex + nx_) + ay * (ey + ny_))
+            qx, qy = me[:, 1:, 0] - nt[:, 1:, 0], me[:, 1:, 1] - nt[:, 1:, 1]               # weights: row k
+            wgt = (2.0 * d - np.sqrt(qx * qx + qy * qy)) / nb
+            C[:, :, mo + i, ix] = ax
+            C[:, :, mo + i, iy] = ay
+            h[:, :, mo + i] = -d / 2 - bb
+            px = px + wq * wgt * ax
+            py = py + wq * wgt * ay
+        qlin = q_own.copy()
+        qlin[:, 1:, ix] = q_own[:, 1:, ix] + px
+        qlin[:, 1:, iy] = q_own[:, 1:, iy] + py
+    return qlin, C, h
+
+
+def lin_advance(prm, z, nx, nu, ns, N, x0, u_prev, traj_local):
+    """Host statement of the family's advance (cmpc_lin_advance_dev): from ``z`` (B, nz) in the reference layout,
+    nxe = nx + ns: x0 <- z[nxe : nxe+nx], u_prev <- z[nxe(N+1) : +nu], traj_local[k] <- (z[k nxe + ix],
+    z[k nxe + iy]).  An agent whose z holds any non-finite value keeps all three.  Returns new (x0, u_prev,
+    traj_local); the arguments are left alone."""
+    z = np.asarray(z, np.float64)
+    ix, iy, nxe = int(prm["ix"]), int(prm["iy"]), nx + ns
+    if z.ndim != 2 or z.shape[1] != nxe * (N + 1) + 2 * nu * N:
+        raise ValueError("z: (batch, (nx+ns)(N+1) + 2 nu N)")
+    x0, u_prev, traj_local = (np.array(a, np.float64) for a in (x0, u_prev, traj_local))
+    ok = np.isfinite(z).all(axis=1)
+    xi = z[:, :nxe * (N + 1)].reshape(-1, N + 1, nxe)
+    x0[ok] = xi[ok, 1, :nx]
+    u_prev[ok] = z[ok, nxe * (N + 1):nxe * (N + 1) + nu]
+    traj_local[ok] = np.stack([xi[ok, :, ix], xi[ok, :, iy]], axis=-1)
+    return x0, u_prev, traj_local
+
+
+def lin_of_di(scen, rows=None):
+    """A ``DIScenario`` in the linear-model family: the arguments of ``lin_rows`` (and of cmpc_lin_build_dev) that
+    give the double-integrator builder's qlin, C, h bit for bit.  Position columns ix, iy = 0, 1; mo = 4 own rows
+    per stage, [-v_x <= -min_vel; v_x <= max_vel; p_y <= hw + lane; -p_y <= hw - lane]; own cost -v_ref q_v on v_x
+    and -lane q_lane on p_y, exact 0.0 elsewhere; min_dist and wq from the scenario's parameters.  ``rows``: the
+    local agents (a slice, default all).  Returns dict(prm, own, nbr, traj, self_offset)."""
+    p, dim, N = scen.params, scen.dim, scen.N
+    sl = slice(0, scen.n_agents) if rows is None else rows
+    lane = np.asarray(scen.lane, np.float64)[sl]
+    B, nx = lane.shape[0], 2 * dim
+    C_own = np.zeros((B, N, 4, nx))
+    C_own[:, :, 0, dim] = -1.0
+    C_own[:, :, 1, dim] = 1.0
+    C_own[:, :, 2, 1] = 1.0
+    C_own[:, :, 3, 1] = -1.0
+    h_own = np.empty((B, N, 4))
+    h_own[:, :, 0] = -p["min_vel"]
+    h_own[:, :, 1] = p["max_vel"]
+    h_own[:, :, 2] = (p["hw"] + lane)[:, None]
+    h_own[:, :, 3] = (p["hw"] - lane)[:, None]
+    qlin_own = np.zeros((B, N + 1, nx))
+    qlin_own[:, :, dim] = -p["v_ref"] * p["q_v"]
+    qlin_own[:, :, 1] = (-lane * p["q_lane"])[:, None]
+    return dict(prm=dict(ix=0, iy=1, min_dist=p["min_dist"], wq=p["wq"]),
+                own=dict(qlin_own=qlin_own, C_own=C_own, h_own=h_own), nbr=np.asarray(scen.nbr)[sl], traj=scen.traj,
+                self_offset=sl.start or 0)
+
+
 def make_di(n_agents, N, nb=2, dim=2, seed=SEED):
     rng = np.random.default_rng(seed)
     nx, nu = 2 * dim, dim

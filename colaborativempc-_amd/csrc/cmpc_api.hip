@@ -907,6 +907,74 @@ int cmpc_di_advance_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_
     return CMPC_OK;
 }
 
+static bool lin_own_ok(const cmpc_lin_dims* d, const int* nbr, const cmpc_lin_own* own) {
+    if (!own || !own->qlin_own) return false;
+    if (d && d->mo > 0 && (!own->C_own || !own->h_own)) return false;
+    return !(d && d->nb > 0 && !nbr);
+}
+
+int cmpc_lin_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                       const cmpc_lin_own* own, const double* traj_all, double* qlin, double* C, double* h,
+                       void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!traj_all || !qlin || !C || !h || !lin_own_ok(d, nbr, own)) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::LinConst c;
+    int rc = lin_const(ctx, prm, d, &c);
+    if (rc != CMPC_OK) return rc;
+    if (d->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    const cmpc::LinPtrs p{nbr, own->qlin_own, own->C_own, own->h_own, traj_all, qlin, C, h};
+    HIP_TRY(cmpc::lin_build_launch(c, p, d->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
+int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+                         const double* z, double* x0, double* u_prev, double* traj_local, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!z || !x0 || !u_prev || !traj_local) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::LinConst c;
+    int rc = lin_const(ctx, prm, d, &c);
+    if (rc != CMPC_OK) return rc;
+    if (ns < 0 || ns > CMPC_MAX_NS || nu < 1 || nu > CMPC_MAX_NU)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (0 <= ns <= 4, 1 <= nu <= 4)");
+    if (d->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    HIP_TRY(cmpc::lin_advance_launch(c, ns, nu, z, x0, u_prev, traj_local, d->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
+int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                       const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* dims,
+                       const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
+                       const cmpc_opts* opts, double* traj_local, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!traj_all || !traj_local || !dims || !in || !out || !out->z || !in->x0 || !in->u_prev || !in->qlin || !in->C ||
+        !in->h || !lin_own_ok(d, nbr, own))
+        return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::LinConst c;
+    int rc = lin_const(ctx, prm, d, &c);
+    if (rc != CMPC_OK) return rc;
+    if (dims->batch != d->batch || dims->N != d->N || dims->nx != d->nx || dims->mc != d->mo + d->nb)
+        return fail(ctx, CMPC_ERR_ARG, "linear-model and solver dimensions differ");
+    // every argument rule of the solver before the first launch (cmpc_solve_mpc_batch_dev repeats them)
+    cmpc::MpcConst mc;
+    const char* msg = nullptr;
+    if ((rc = cmpc::mpc_prepare(dims, w, opts, &mc, &msg)) != CMPC_OK) return fail(ctx, rc, msg);
+    if (opts && (opts->flags & CMPC_FLAG_LPV_AUTO) && !(opts->flags & CMPC_FLAG_LPV))
+        return fail(ctx, CMPC_ERR_ARG, "CMPC_FLAG_LPV_AUTO needs a host wait, so a device-pointer entry cannot take it: "
+                                       "run cmpc_mpc_lpv_level_dev and pass CMPC_FLAG_LPV");
+    if (d->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const cmpc::LinPtrs p{nbr, own->qlin_own, own->C_own, own->h_own, traj_all, const_cast<double*>(in->qlin),
+                          const_cast<double*>(in->C), const_cast<double*>(in->h)};
+    HIP_TRY(cmpc::lin_build_launch(c, p, d->batch, s));
+    if ((rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream)) != CMPC_OK) return rc;
+    HIP_TRY(cmpc::lin_advance_launch(c, dims->ns, dims->nu, out->z, const_cast<double*>(in->x0),
+                                     const_cast<double*>(in->u_prev), traj_local, d->batch, s));
+    return CMPC_OK;
+}
+
 int cmpc_solve_qp_batch(cmpc_ctx* ctx, const cmpc_qp_dims* d, const cmpc_qp_data* in, const cmpc_qp_out* out,
                         const cmpc_opts* opts) {
     if (!ctx) return CMPC_ERR_ARG;

@@ -1,5 +1,6 @@
-// The C ABI's context object and the error helpers shared by the host-side translation units
-// (cmpc_api.hip, rounds_api.hip, round_log.hip).  Not part of the public header: cmpc.h keeps cmpc_ctx opaque.
+// The C ABI's context object, the error helpers and the linear-model family's dimension rules shared by the
+// host-side translation units (cmpc_api.hip, rounds_api.hip, round_log.hip).  Not part of the public header:
+// cmpc.h keeps cmpc_ctx opaque.
 #pragma once
 #include <string>
 
@@ -26,6 +27,18 @@ inline int fail(cmpc_ctx* c, int code, const std::string& msg) {
 
 inline int hip_fail(cmpc_ctx* c, hipError_t e, const char* where) {
     return fail(c, CMPC_ERR_DEVICE, std::string(where) + ": " + hipGetErrorString(e));
+}
+
+// the dimension rules of the linear-model family (cmpc_lin_*); no device call
+inline int lin_const(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, cmpc::LinConst* c) {
+    if (!prm || !d) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    if (d->nx < 1 || d->nx > CMPC_MAX_NX || prm->ix < 0 || prm->ix >= d->nx || prm->iy < 0 || prm->iy >= d->nx ||
+        prm->ix == prm->iy)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (1 <= nx <= 12, position columns ix != iy in [0, nx))");
+    if (d->N < 1 || d->nb < 0 || d->mo < 0 || d->mo + d->nb > CMPC_MAX_MC || d->batch < 0 || d->self_offset < 0)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (N >= 1, mo + nb <= 16, batch >= 0, self_offset >= 0)");
+    *c = cmpc::LinConst{d->N, d->nb, d->nx, d->mo, prm->ix, prm->iy, d->self_offset, prm->min_dist, prm->wq};
+    return CMPC_OK;
 }
 
 #define HIP_TRY(expr)                                              \

@@ -352,6 +352,27 @@ hipError_t di_build_launch(const DiConst& c, const DiPtrs& p, int batch, hipStre
 hipError_t di_advance_launch(const DiConst& c, const double* z, double* x0, double* up, double* traj, int batch,
                              hipStream_t s);
 
+// Rounds for any linear agent model (lin_build.hip): own rows / cost copied, nb planes and the coverage term
+// appended (the arithmetic of di_rows.h); the advance skips an agent whose z is not finite.
+
+struct LinConst {
+    int N, nb, nx, mo, ix, iy, self_offset;
+    double min_dist, wq;
+};
+
+struct LinPtrs {
+    const int* nbr;
+    const double *qlin_own, *C_own, *h_own;
+    const double* traj_all;
+    double* qlin;
+    double* C;
+    double* h;
+};
+
+hipError_t lin_build_launch(const LinConst& c, const LinPtrs& p, int batch, hipStream_t s);
+hipError_t lin_advance_launch(const LinConst& c, int ns, int nu, const double* z, double* x0, double* up,
+                              double* traj, int batch, hipStream_t s);
+
 hipError_t selftest_mfma_launch(const double* A, const double* B, double* D, hipStream_t s);
 hipError_t selftest_fma_bcast_launch(const double* A, const double* X, const double* C, const double* one,
                                      const double* nzero, double* fused, double* ref, hipStream_t s);

@@ -1,0 +1,112 @@
+// Consensus rounds for any linear agent model (include/cmpc.h, cmpc_lin_*): the per-round rebuild and the
+// round advance of an agent given by its own stage rows C_own / h_own (mo per stage), its own linear cost
+// qlin_own and the two state columns ix, iy of its position.  The builder is di_stage_rows (di_rows.h) with
+// the four constant rows and the two constant cost entries moved into the caller's arrays: the hyperplane
+// arithmetic of compute_plane.py:41-68 and the coverage weights of misc.py:10-18 in the same operation
+// order, so the double-integrator family is the special case ix, iy = 0, 1, mo = 4, bit for bit.
+//   rows per stage k=1..N  [ C_own rows (mo) ; a_i . p <= -d/2 - b_i  (i < nb) ]
+//   planes from row k-1 of the previous trajectories, weights from row k
+//   p_k = qlin_own_k + wq sum_i w_i a_i on (ix, iy)
+// One workgroup (one wavefront) per agent, no LDS, no scratch: the copies go lane by lane over consecutive
+// addresses, the planes one lane per stage with the neighbours in order.
+#include <cmath>
+
+#include "internal.h"
+
+namespace cmpc {
+
+namespace {
+
+__global__ __launch_bounds__(kWave) void lin_build_kernel(const LinConst c, const LinPtrs P) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x;
+    const int N = c.N, nx = c.nx, mo = c.mo, nb = c.nb, mc = mo + nb, ix = c.ix, iy = c.iy;
+    const double* own = P.traj_all + (size_t)(c.self_offset + b) * (N + 1) * 2;
+    const int* nbr = P.nbr + (size_t)b * nb;
+    const double* qo = P.qlin_own + (size_t)b * (N + 1) * nx;
+    const double* Co = P.C_own + (size_t)b * N * mo * nx;  // (not dereferenced when mo == 0)
+    const double* ho = P.h_own + (size_t)b * N * mo;
+    double* qlin = P.qlin + (size_t)b * (N + 1) * nx;
+    double* C = P.C + (size_t)b * N * mc * nx;
+    double* h = P.h + (size_t)b * N * mc;
+
+    // the own cost, except the two position entries of stages 1..N (the stage lanes below write those)
+    for (int i = threadIdx.x; i < (N + 1) * nx; i += kWave) {
+        const int s = i % nx;
+        if (i < nx || (s != ix && s != iy)) qlin[i] = qo[i];
+    }
+    // the own rows, and the zeros of the plane rows (their ix, iy entries: the stage lanes)
+    for (int i = threadIdx.x; i < N * mc * nx; i += kWave) {
+        const int s = i % nx, kr = i / nx, r = kr % mc, k1 = kr / mc;
+        if (r < mo)
+            C[i] = Co[((size_t)k1 * mo + r) * nx + s];
+        else if (s != ix && s != iy)
+            C[i] = 0.0;
+    }
+    for (int i = threadIdx.x; i < N * mc; i += kWave) {
+        const int r = i % mc, k1 = i / mc;
+        if (r < mo) h[i] = ho[(size_t)k1 * mo + r];
+    }
+    // stage k = 1..N: the nb planes (row k-1 of the trajectories) and the coverage term (row k)
+    for (int k = threadIdx.x + 1; k <= N; k += kWave) {
+        const int h1 = k - 1;
+        double* Ck = C + ((size_t)h1 * mc + mo) * nx;
+        double* hk = h + (size_t)h1 * mc + mo;
+        double px = 0.0, py = 0.0;
+        for (int i = 0; i < nb; ++i) {
+            const double* nt = P.traj_all + (size_t)nbr[i] * (N + 1) * 2;
+            const double ex = own[h1 * 2], ey = own[h1 * 2 + 1];
+            const double nx_ = nt[h1 * 2], ny_ = nt[h1 * 2 + 1];
+            const double dx = nx_ - ex, dy = ny_ - ey;
+            const double nrm = sqrt(dx * dx + dy * dy);
+            const double ax = dx / nrm, ay = dy / nrm;
+            const double bb = -0.5 * (ax * (ex + nx_) + ay * (ey + ny_));
+            const double qx = own[k * 2] - nt[k * 2], qy = own[k * 2 + 1] - nt[k * 2 + 1];
+            const double wgt = (2.0 * c.min_dist - sqrt(qx * qx + qy * qy)) / nb;
+            Ck[(size_t)i * nx + ix] = ax;
+            Ck[(size_t)i * nx + iy] = ay;
+            hk[i] = -c.min_dist / 2 - bb;
+            px = px + c.wq * wgt * ax;
+            py = py + c.wq * wgt * ay;
+        }
+        qlin[(size_t)k * nx + ix] = qo[(size_t)k * nx + ix] + px;
+        qlin[(size_t)k * nx + iy] = qo[(size_t)k * nx + iy] + py;
+    }
+}
+
+// x0 <- x_1, u_prev <- u_0, traj <- predicted (z[ix], z[iy]) for k = 0..N  (z in reference layout); an agent
+// with a non-finite z keeps all three (no NaN reaches a neighbour: the LPV advance's rule)
+__global__ __launch_bounds__(kWave) void lin_advance_kernel(const LinConst c, int ns, int nu,
+                                                            const double* __restrict__ z, double* x0, double* up,
+                                                            double* traj) {
+    const int b = blockIdx.x;
+    const int N = c.N, nx = c.nx, nxe = nx + ns;
+    const size_t nz = (size_t)nxe * (N + 1) + 2 * (size_t)nu * N;
+    const double* zb = z + (size_t)b * nz;
+    bool bad = false;
+    for (size_t i = threadIdx.x; i < nz; i += kWave) bad |= !isfinite(zb[i]);
+    if (__any(bad)) return;  // (the workgroup is one wavefront)
+    for (int i = threadIdx.x; i < 2 * (N + 1); i += kWave) {
+        const int k = i >> 1;
+        traj[(size_t)b * 2 * (N + 1) + i] = zb[(size_t)k * nxe + ((i & 1) ? c.iy : c.ix)];
+    }
+    if ((int)threadIdx.x < nx) x0[(size_t)b * nx + threadIdx.x] = zb[nxe + threadIdx.x];
+    if ((int)threadIdx.x < nu) up[(size_t)b * nu + threadIdx.x] = zb[(size_t)nxe * (N + 1) + threadIdx.x];
+}
+
+}  // namespace
+
+hipError_t lin_build_launch(const LinConst& c, const LinPtrs& p, int batch, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(lin_build_kernel, dim3(batch), dim3(kWave), 0, s, c, p);
+    return hipGetLastError();
+}
+
+hipError_t lin_advance_launch(const LinConst& c, int ns, int nu, const double* z, double* x0, double* up,
+                              double* traj, int batch, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(lin_advance_kernel, dim3(batch), dim3(kWave), 0, s, c, ns, nu, z, x0, up, traj);
+    return hipGetLastError();
+}
+
+}  // namespace cmpc

@@ -4,17 +4,20 @@
 // chains the C-ABI device entry points on the context's stream:
 //   LPV: [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
 //   DI:  [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
+//   LIN: [cmpc_nbr_select_dev ->] cmpc_lin_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's communicator
 // (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).  With the log on
 // (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1] into the
 // handle's log ring, and an event pair brackets its solver call.
 //
-// What the two families share lives once, in RoundsCore and the functions on it: the create checks, the device
-// block, the re-selection, the exchange, get / set_traj, destroy and the log.  The two step loops stay apart
-// (their middles differ), and so do their error paths: the LPV step returns at once, without a host
-// synchronisation, and counts a round only after its exchange and log rows; the DI step counts a round as soon
-// as its solver call and launch order are queued (its outputs exist whatever the exchange returns), leaves the
-// loop at the first error and synchronises the host once before it returns the error.
+// What the families share lives once, in RoundsCore and the functions on it: the create checks, the device
+// block, the re-selection, the exchange, get / set_traj, destroy and the log.  The DI and the linear-model (LIN)
+// handles also share SolverRounds: the structured problem they hand cmpc_solve_mpc_batch_dev, the history ring,
+// the step loop around the family's round entry, read and history.  The LPV step loop stays apart (its middle
+// differs), and so does its error path: the LPV step returns at once, without a host synchronisation, and counts
+// a round only after its exchange and log rows; the DI / LIN step counts a round as soon as its solver call and
+// launch order are queued (its outputs exist whatever the exchange returns), leaves the loop at the first error
+// and synchronises the host once before it returns the error.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -94,8 +97,8 @@ struct cmpc_lpv_rounds : RoundsCore {
     int *iters = nullptr, *status = nullptr, *infeasible = nullptr;
 };
 
-struct cmpc_di_rounds : RoundsCore {
-    cmpc_di_params prm{};
+// What the handles around cmpc_solve_mpc_batch_dev (DI, LIN) are made of.
+struct SolverRounds : RoundsCore {
     int history = 1;  // round r writes row r % history of kkt / iters / status
     cmpc_mpc_dims md{};
     // copy of the batch-shared weights (cmpc_mpc_weights holds host pointers)
@@ -103,21 +106,34 @@ struct cmpc_di_rounds : RoundsCore {
         Qs[CMPC_MAX_NS]{}, u_ub[CMPC_MAX_NU]{}, u_lb[CMPC_MAX_NU]{};
     int row_slack[CMPC_MAX_MC]{}, row_sign[CMPC_MAX_MC]{};
     cmpc_mpc_weights w{};
-    double *A = nullptr, *B = nullptr, *x0 = nullptr, *u_prev = nullptr, *lane = nullptr, *qlin = nullptr,
-           *C = nullptr, *h = nullptr, *z = nullptr, *kkt = nullptr;
+    double *A = nullptr, *B = nullptr, *x0 = nullptr, *u_prev = nullptr, *qlin = nullptr, *C = nullptr, *h = nullptr,
+           *z = nullptr, *kkt = nullptr;
     int *iters = nullptr, *status = nullptr, *order = nullptr;
+};
+
+struct cmpc_di_rounds : SolverRounds {
+    cmpc_di_params prm{};
+    double* lane = nullptr;
+};
+
+struct cmpc_lin_rounds : SolverRounds {
+    cmpc_lin_params prm{};
+    int mo = 0;
+    double *qlin_own = nullptr, *C_own = nullptr, *h_own = nullptr;  // uploaded once, only read
 };
 
 namespace {
 
 size_t nz_lpv(int N) { return 12 * (size_t)(N + 1) + 4 * (size_t)N; }
-size_t nz_di(int nx, int nu, int N) { return (size_t)(nx + 3) * (N + 1) + 2 * (size_t)nu * N; }
+size_t nz_mpc(const cmpc_mpc_dims& d) { return (size_t)(d.nx + d.ns) * (d.N + 1) + 2 * (size_t)d.nu * d.N; }
 
 // ---- create ----
 
-// The create checks both families share (`nbr`: init->nbr); CMPC_OK, or CMPC_ERR_ARG with the message set.
-int check_create(cmpc_ctx* ctx, const cmpc_lpv_rounds_dims& d, int known_flags, const int* nbr, const cmpc_opts* opts) {
-    if (d.N < 1 || d.nb < 0 || 4 + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
+// The create checks the families share (`nbr`: init->nbr; `own_rows`: the stage rows before the nb planes);
+// CMPC_OK, or CMPC_ERR_ARG with the message set.
+int check_create(cmpc_ctx* ctx, const cmpc_lpv_rounds_dims& d, int known_flags, const int* nbr, const cmpc_opts* opts,
+                 int own_rows = 4) {
+    if (d.N < 1 || d.nb < 0 || own_rows + d.nb > CMPC_MAX_MC || d.batch < 1 || d.n_total < d.batch || d.self_offset < 0 ||
         d.self_offset + d.batch > d.n_total)
         return fail(ctx, CMPC_ERR_ARG, "bad rounds dimensions (1 <= batch, self_offset + batch <= n_total, nb <= 12)");
     if (d.flags & ~known_flags) return fail(ctx, CMPC_ERR_ARG, "unknown rounds flag");
@@ -239,8 +255,8 @@ int destroy(Handle* h) {
 
 // ---- the log ----
 
-// nx, nu, look_col: the family's state and input widths and its look-ahead column
-int log_enable(RoundsCore* h, int capacity, int flags, int nx, int nu, int look_col) {
+// nx, nu, look_col, ns: the family's state and input widths, its look-ahead column and its slacks
+int log_enable(RoundsCore* h, int capacity, int flags, int nx, int nu, int look_col, int ns = 3) {
     if (!h) return CMPC_ERR_ARG;
     cmpc_ctx* ctx = h->ctx;
     const cmpc_lpv_rounds_dims& d = h->d;
@@ -258,7 +274,7 @@ int log_enable(RoundsCore* h, int capacity, int flags, int nx, int nu, int look_
     lg->capacity = capacity;
     lg->flags = flags;
     lg->first = lg->end = h->rounds_done;
-    lg->d = cmpc_log_dims{d.batch, nx, nu, 3, d.N, look_col};
+    lg->d = cmpc_log_dims{d.batch, nx, nu, ns, d.N, look_col};
     lg->sel = cmpc_nbr_dims{d.batch, d.N, 1, d.self_offset, d.n_total, 0, 0};
     const size_t rows = (size_t)capacity * d.batch, sep_rows = sep ? rows : 0;
     const size_t bytes = device_block(&lg->mem, {{lg->state, rows * nx}, {lg->u, rows * nu}, {lg->look, rows},
@@ -359,6 +375,110 @@ int log_read(RoundsCore* h, int first_round, int count, const cmpc_rounds_log* o
         HIP_TRY(hipEventElapsedTime(&ms, lg->ev[2 * row], lg->ev[2 * row + 1]));
         o->solve_ms[i] = ms;
     }
+    return CMPC_OK;
+}
+
+// ---- the handles around cmpc_solve_mpc_batch_dev (DI, LIN) ----
+
+// the batch-shared weights of `w` (md is set), copied into the handle
+void copy_weights(SolverRounds* h, const cmpc_mpc_weights* w) {
+    const int nx = h->md.nx, nu = h->md.nu, ns = h->md.ns, mc = h->md.mc;
+    std::memcpy(h->Q, w->Q, sizeof(double) * nx * nx);
+    std::memcpy(h->R, w->R, sizeof(double) * nu * nu);
+    std::memcpy(h->dR, w->dR, sizeof(double) * nu * nu);
+    std::memcpy(h->Qs, w->Qs, sizeof(double) * ns);
+    std::memcpy(h->u_ub, w->u_ub, sizeof(double) * nu);
+    std::memcpy(h->u_lb, w->u_lb, sizeof(double) * nu);
+    std::memcpy(h->row_slack, w->row_slack, sizeof(int) * mc);
+    std::memcpy(h->row_sign, w->row_sign, sizeof(int) * mc);
+    h->w = cmpc_mpc_weights{h->Q, h->R, h->dR, h->Qs, h->u_ub, h->u_lb, h->row_slack, h->row_sign};
+}
+
+// The step loop: `round_call(data, out, stream)` is the family's round entry (build, solve, advance) on the
+// handle's buffers, `out` this round's row of the history ring; `where`: the entry's name for a device error.
+template <class Round>
+int step_rounds(SolverRounds* h, int rounds, int* rounds_done, const char* where, Round round_call) {
+    cmpc_ctx* ctx = h->ctx;
+    if (rounds_done) *rounds_done = 0;
+    int done = 0, rc;
+    if ((rc = check_step(h, rounds)) != CMPC_OK) return rc;
+    const bool lpt = h->d.flags & CMPC_ROUNDS_LPT;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const cmpc_mpc_data din{h->A, h->B, h->x0, h->u_prev, h->qlin, h->C, h->h};
+    for (int r = 0; r < rounds && rc == CMPC_OK; ++r) {
+        const int round = h->rounds_done;
+        const size_t slot = (size_t)(round % h->history) * h->d.batch;  // this round's row of the history ring
+        const cmpc_mpc_out dout{h->z, h->kkt + slot, h->iters + slot, h->status + slot};
+        if ((rc = reselect(h, s)) != CMPC_OK) break;
+        h->opts.order = (lpt && round > 0) ? h->order : nullptr;
+        hipError_t ev = log_mark(h->log, round, 0, s);
+        if (ev == hipSuccess) {
+            if ((rc = round_call(&din, &dout, s)) != CMPC_OK) {
+                log_abandon(h->log, round);
+                break;
+            }
+            ev = log_mark(h->log, round, 1, s);
+        }
+        if (ev != hipSuccess) {
+            rc = hip_fail(ctx, ev, where);
+            break;
+        }
+        // the next round's launch order, stream-ordered after this solve
+        if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) break;
+        ++h->rounds_done;  // the round's outputs exist from here on, whatever the exchange returns
+        ++done;
+        // the log's rows of this round, from the history-ring row the solver wrote
+        if ((rc = exchange(h, s)) == CMPC_OK)
+            rc = log_round(h, round, h->z, h->kkt + slot, h->iters + slot, h->status + slot, s);
+    }
+    // one host synchronisation, also after an error: the rounds already queued have then finished
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rounds_done) *rounds_done = done;
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(e);
+    return CMPC_OK;
+}
+
+// Out: cmpc_di_rounds_out / cmpc_lin_rounds_out (the same members)
+template <class Out>
+int read_rounds(SolverRounds* h, const Out* o) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    const size_t slot = (size_t)((h->rounds_done > 0 ? h->rounds_done - 1 : 0) % h->history) * B;
+    auto dn = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s); };
+    if (o->z) HIP_TRY(dn(o->z, h->z, 8 * B * nz_mpc(h->md)));
+    if (o->kkt) HIP_TRY(dn(o->kkt, h->kkt + slot, 8 * B));
+    if (o->iters) HIP_TRY(dn(o->iters, h->iters + slot, 4 * B));
+    if (o->status) HIP_TRY(dn(o->status, h->status + slot, 4 * B));
+    if (o->x0) HIP_TRY(dn(o->x0, h->x0, 8 * B * h->md.nx));
+    if (o->u_prev) HIP_TRY(dn(o->u_prev, h->u_prev, 8 * B * h->md.nu));
+    if (o->nbr && h->d.nb) HIP_TRY(dn(o->nbr, h->nbr, 4 * B * h->d.nb));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
+int history_rounds(SolverRounds* h, int first_round, int count, double* kkt, int* iters, int* status) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (first_round < 0 || count < 0 || (long long)first_round + count > h->rounds_done)
+        return fail(ctx, CMPC_ERR_ARG, "history: a round that has not run yet");
+    if (count > 0 && first_round < h->rounds_done - h->history)
+        return fail(ctx, CMPC_ERR_ARG, "history: a round the ring has already overwritten (dims.history rounds are kept)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    for (int i = 0; i < count; ++i) {
+        const size_t slot = (size_t)((first_round + i) % h->history) * B;
+        if (kkt) HIP_TRY(hipMemcpyAsync(kkt + i * B, h->kkt + slot, 8 * B, hipMemcpyDeviceToHost, s));
+        if (iters) HIP_TRY(hipMemcpyAsync(iters + i * B, h->iters + slot, 4 * B, hipMemcpyDeviceToHost, s));
+        if (status) HIP_TRY(hipMemcpyAsync(status + i * B, h->status + slot, 4 * B, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
     return CMPC_OK;
 }
 
@@ -543,22 +663,14 @@ int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_m
     // time-invariant agents (the handle never changes A or B after this): the promise the solver may use
     if (stages_lti(in->A, d.batch, d.N, (size_t)nx * nx) && stages_lti(in->B, d.batch, d.N, (size_t)nx * nu))
         h->opts.flags |= CMPC_FLAG_LTI;
-    std::memcpy(h->Q, w->Q, sizeof(double) * nx * nx);
-    std::memcpy(h->R, w->R, sizeof(double) * nu * nu);
-    std::memcpy(h->dR, w->dR, sizeof(double) * nu * nu);
-    std::memcpy(h->Qs, w->Qs, sizeof(double) * 3);
-    std::memcpy(h->u_ub, w->u_ub, sizeof(double) * nu);
-    std::memcpy(h->u_lb, w->u_lb, sizeof(double) * nu);
-    std::memcpy(h->row_slack, w->row_slack, sizeof(int) * mc);
-    std::memcpy(h->row_sign, w->row_sign, sizeof(int) * mc);
-    h->w = cmpc_mpc_weights{h->Q, h->R, h->dR, h->Qs, h->u_ub, h->u_lb, h->row_slack, h->row_sign};
+    copy_weights(h, w);
 
     const size_t B = d.batch, N = d.N, nb1 = d.nb ? d.nb : 1, T = d.n_total, row = h->traj_row(), H = h->history;
     const size_t nA = B * N * nx * nx, nB = B * N * nx * nu;
     const size_t bytes = device_block(
         &h->mem, {{h->A, nA}, {h->B, nB}, {h->x0, B * nx}, {h->u_prev, B * nu}, {h->lane, B}, {h->traj_all, T * row},
                   {h->traj_local, B * row}, {h->qlin, B * (N + 1) * nx}, {h->C, B * N * mc * nx}, {h->h, B * N * mc},
-                  {h->z, B * nz_di(nx, nu, d.N)}, {h->kkt, H * B}, {h->nbr, B * nb1}, {h->iters, H * B},
+                  {h->z, B * nz_mpc(h->md)}, {h->kkt, H * B}, {h->nbr, B * nb1}, {h->iters, H * B},
                   {h->status, H * B}, {h->order, B}});
     if (!bytes) {
         delete h;
@@ -584,88 +696,18 @@ int cmpc_di_rounds_create(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_m
 
 int cmpc_di_rounds_step(cmpc_di_rounds* h, int rounds, int* rounds_done) {
     if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (rounds_done) *rounds_done = 0;
-    int done = 0, rc;
-    if ((rc = check_step(h, rounds)) != CMPC_OK) return rc;
-    const bool lpt = h->d.flags & CMPC_ROUNDS_LPT;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     const cmpc_di_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset};
-    const cmpc_mpc_data din{h->A, h->B, h->x0, h->u_prev, h->qlin, h->C, h->h};
-    for (int r = 0; r < rounds && rc == CMPC_OK; ++r) {
-        const int round = h->rounds_done;
-        const size_t slot = (size_t)(round % h->history) * h->d.batch;  // this round's row of the history ring
-        const cmpc_mpc_out dout{h->z, h->kkt + slot, h->iters + slot, h->status + slot};
-        if ((rc = reselect(h, s)) != CMPC_OK) break;
-        h->opts.order = (lpt && round > 0) ? h->order : nullptr;
-        hipError_t ev = log_mark(h->log, round, 0, s);
-        if (ev == hipSuccess) {
-            if ((rc = cmpc_di_round_dev(ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w, &din, &dout,
-                                        &h->opts, h->traj_local, s)) != CMPC_OK) {
-                log_abandon(h->log, round);
-                break;
-            }
-            ev = log_mark(h->log, round, 1, s);
-        }
-        if (ev != hipSuccess) {
-            rc = hip_fail(ctx, ev, "cmpc_di_rounds_step: log event");
-            break;
-        }
-        // the next round's launch order, stream-ordered after this solve
-        if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) break;
-        ++h->rounds_done;  // the round's outputs exist from here on, whatever the exchange returns
-        ++done;
-        // the log's rows of this round, from the history-ring row the solver wrote
-        if ((rc = exchange(h, s)) == CMPC_OK)
-            rc = log_round(h, round, h->z, h->kkt + slot, h->iters + slot, h->status + slot, s);
-    }
-    // one host synchronisation, also after an error: the rounds already queued have then finished
-    const hipError_t e = hipStreamSynchronize(s);
-    if (rounds_done) *rounds_done = done;
-    if (rc != CMPC_OK) return rc;
-    HIP_TRY(e);
-    return CMPC_OK;
+    return step_rounds(h, rounds, rounds_done, "cmpc_di_rounds_step: log event",
+                       [&](const cmpc_mpc_data* din, const cmpc_mpc_out* dout, hipStream_t s) {
+                           return cmpc_di_round_dev(h->ctx, &h->prm, &rd, h->nbr, h->lane, h->traj_all, &h->md, &h->w,
+                                                    din, dout, &h->opts, h->traj_local, s);
+                       });
 }
 
-int cmpc_di_rounds_read(cmpc_di_rounds* h, const cmpc_di_rounds_out* o) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t B = h->d.batch;
-    const size_t slot = (size_t)((h->rounds_done > 0 ? h->rounds_done - 1 : 0) % h->history) * B;
-    auto dn = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s); };
-    if (o->z) HIP_TRY(dn(o->z, h->z, 8 * B * nz_di(h->md.nx, h->md.nu, h->d.N)));
-    if (o->kkt) HIP_TRY(dn(o->kkt, h->kkt + slot, 8 * B));
-    if (o->iters) HIP_TRY(dn(o->iters, h->iters + slot, 4 * B));
-    if (o->status) HIP_TRY(dn(o->status, h->status + slot, 4 * B));
-    if (o->x0) HIP_TRY(dn(o->x0, h->x0, 8 * B * h->md.nx));
-    if (o->u_prev) HIP_TRY(dn(o->u_prev, h->u_prev, 8 * B * h->md.nu));
-    if (o->nbr && h->d.nb) HIP_TRY(dn(o->nbr, h->nbr, 4 * B * h->d.nb));
-    HIP_TRY(hipStreamSynchronize(s));
-    return CMPC_OK;
-}
+int cmpc_di_rounds_read(cmpc_di_rounds* h, const cmpc_di_rounds_out* o) { return read_rounds(h, o); }
 
 int cmpc_di_rounds_history(cmpc_di_rounds* h, int first_round, int count, double* kkt, int* iters, int* status) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (first_round < 0 || count < 0 || (long long)first_round + count > h->rounds_done)
-        return fail(ctx, CMPC_ERR_ARG, "history: a round that has not run yet");
-    if (count > 0 && first_round < h->rounds_done - h->history)
-        return fail(ctx, CMPC_ERR_ARG, "history: a round the ring has already overwritten (dims.history rounds are kept)");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t B = h->d.batch;
-    for (int i = 0; i < count; ++i) {
-        const size_t slot = (size_t)((first_round + i) % h->history) * B;
-        if (kkt) HIP_TRY(hipMemcpyAsync(kkt + i * B, h->kkt + slot, 8 * B, hipMemcpyDeviceToHost, s));
-        if (iters) HIP_TRY(hipMemcpyAsync(iters + i * B, h->iters + slot, 4 * B, hipMemcpyDeviceToHost, s));
-        if (status) HIP_TRY(hipMemcpyAsync(status + i * B, h->status + slot, 4 * B, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return CMPC_OK;
+    return history_rounds(h, first_round, count, kkt, iters, status);
 }
 
 int cmpc_di_rounds_get_traj(cmpc_di_rounds* h, double* traj_local) { return get_traj(h, traj_local); }
@@ -676,6 +718,116 @@ int cmpc_di_rounds_log_enable(cmpc_di_rounds* h, int capacity, int flags) {
 }
 int cmpc_di_rounds_log_range(cmpc_di_rounds* h, int* first_round, int* count) { return log_range(h, first_round, count); }
 int cmpc_di_rounds_log_read(cmpc_di_rounds* h, int first_round, int count, const cmpc_rounds_log* o) {
+    return log_read(h, first_round, count, o);
+}
+
+// ---- agents of any linear model (cmpc_lin_rounds_*): the DI handle with the caller's own rows and cost ----
+
+int cmpc_lin_rounds_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights* w,
+                           const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_init* in, const cmpc_opts* opts,
+                           cmpc_lin_rounds** out) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    *out = nullptr;
+    const cmpc_lpv_rounds_dims d{dims->n_total, dims->batch, dims->self_offset, dims->N, dims->nb, dims->flags};
+    const cmpc_lin_dims ld{d.batch, d.N, d.nb, d.self_offset, dims->nx, dims->mo};
+    cmpc::LinConst lc;
+    int rc = lin_const(ctx, prm, &ld, &lc);  // the family's own dimension rules first: mo is checked before it is used
+    if (rc != CMPC_OK) return rc;
+    if (dims->nu < 1 || dims->nu > CMPC_MAX_NU || dims->ns < 0 || dims->ns > CMPC_MAX_NS)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (0 <= ns <= 4, 1 <= nu <= 4)");
+    rc = check_create(ctx, d, CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT,
+                      in->nbr, opts, dims->mo);
+    if (rc != CMPC_OK) return rc;
+    if (dims->history < 0) return fail(ctx, CMPC_ERR_ARG, "negative history");
+    if (!w->Q || !w->R || !w->dR || (dims->ns && !w->Qs) || !w->u_ub || !w->u_lb ||
+        (dims->mo + d.nb && (!w->row_slack || !w->row_sign)))
+        return fail(ctx, CMPC_ERR_ARG, "null weights");
+    if (!in->A || !in->B || !in->x0 || !in->u_prev || !in->qlin_own || !in->traj || (dims->mo && (!in->C_own || !in->h_own)))
+        return fail(ctx, CMPC_ERR_ARG, "null initial state");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    auto* h = new cmpc_lin_rounds();
+    core_init(h, ctx, d, opts);
+    h->prm = *prm;
+    h->mo = dims->mo;
+    h->history = std::max(dims->history, 1);
+    const int nx = dims->nx, nu = dims->nu, mo = dims->mo, mc = mo + d.nb;
+    h->md = cmpc_mpc_dims{nx, nu, d.N, dims->ns, mc, d.batch};
+    // time-invariant agents (the handle never changes A or B after this): the promise the solver may use
+    if (stages_lti(in->A, d.batch, d.N, (size_t)nx * nx) && stages_lti(in->B, d.batch, d.N, (size_t)nx * nu))
+        h->opts.flags |= CMPC_FLAG_LTI;
+    copy_weights(h, w);
+
+    const size_t B = d.batch, N = d.N, nb1 = d.nb ? d.nb : 1, T = d.n_total, row = h->traj_row(), H = h->history;
+    const size_t nA = B * N * nx * nx, nB = B * N * nx * nu, nq = B * (N + 1) * nx, nC = B * N * mo * nx, nh = B * N * mo;
+    const size_t bytes = device_block(
+        &h->mem, {{h->A, nA}, {h->B, nB}, {h->x0, B * nx}, {h->u_prev, B * nu}, {h->qlin_own, nq}, {h->C_own, nC},
+                  {h->h_own, nh}, {h->traj_all, T * row}, {h->traj_local, B * row}, {h->qlin, nq},
+                  {h->C, B * N * mc * nx}, {h->h, B * N * mc}, {h->z, B * nz_mpc(h->md)}, {h->kkt, H * B},
+                  {h->nbr, B * nb1}, {h->iters, H * B}, {h->status, H * B}, {h->order, B}});
+    if (!bytes) {
+        delete h;
+        return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
+    }
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemsetAsync(h->mem, 0, bytes, s);  // a read before the first round returns zeros
+    if (e == hipSuccess) e = upload(h->A, in->A, 8 * nA, s);
+    if (e == hipSuccess) e = upload(h->B, in->B, 8 * nB, s);
+    if (e == hipSuccess) e = upload(h->x0, in->x0, 8 * B * nx, s);
+    if (e == hipSuccess) e = upload(h->u_prev, in->u_prev, 8 * B * nu, s);
+    if (e == hipSuccess) e = upload(h->qlin_own, in->qlin_own, 8 * nq, s);
+    if (e == hipSuccess && mo) e = upload(h->C_own, in->C_own, 8 * nC, s);
+    if (e == hipSuccess && mo) e = upload(h->h_own, in->h_own, 8 * nh, s);
+    if (e == hipSuccess) e = upload(h->traj_all, in->traj, 8 * T * row, s);
+    if (e == hipSuccess && d.nb) e = upload(h->nbr, in->nbr, 4 * B * d.nb, s);
+    if ((e = finish_uploads(h, e)) != hipSuccess) {
+        (void)hipFree(h->mem);
+        delete h;
+        return hip_fail(ctx, e, "cmpc_lin_rounds_create: upload");
+    }
+    *out = h;
+    return CMPC_OK;
+}
+
+int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
+    if (!h) return CMPC_ERR_ARG;
+    const cmpc_lin_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->md.nx, h->mo};
+    const cmpc_lin_own own{h->qlin_own, h->C_own, h->h_own};
+    return step_rounds(h, rounds, rounds_done, "cmpc_lin_rounds_step: log event",
+                       [&](const cmpc_mpc_data* din, const cmpc_mpc_out* dout, hipStream_t s) {
+                           return cmpc_lin_round_dev(h->ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, &h->md, &h->w,
+                                                     din, dout, &h->opts, h->traj_local, s);
+                       });
+}
+
+int cmpc_lin_rounds_read(cmpc_lin_rounds* h, const cmpc_lin_rounds_out* o) { return read_rounds(h, o); }
+
+int cmpc_lin_rounds_history(cmpc_lin_rounds* h, int first_round, int count, double* kkt, int* iters, int* status) {
+    return history_rounds(h, first_round, count, kkt, iters, status);
+}
+
+// the measured state of a real loop replaces the predicted one (HOST pointers, either may be NULL)
+int cmpc_lin_rounds_set_state(cmpc_lin_rounds* h, const double* x0, const double* u_prev) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    if (x0) HIP_TRY(upload(h->x0, x0, 8 * B * h->md.nx, s));
+    if (u_prev) HIP_TRY(upload(h->u_prev, u_prev, 8 * B * h->md.nu, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
+}
+
+int cmpc_lin_rounds_get_traj(cmpc_lin_rounds* h, double* traj_local) { return get_traj(h, traj_local); }
+int cmpc_lin_rounds_set_traj(cmpc_lin_rounds* h, const double* traj_all) { return set_traj(h, traj_all); }
+int cmpc_lin_rounds_destroy(cmpc_lin_rounds* h) { return destroy(h); }
+int cmpc_lin_rounds_log_enable(cmpc_lin_rounds* h, int capacity, int flags) {
+    return h ? log_enable(h, capacity, flags, h->md.nx, h->md.nu, h->prm.ix, h->md.ns) : CMPC_ERR_ARG;
+}
+int cmpc_lin_rounds_log_range(cmpc_lin_rounds* h, int* first_round, int* count) { return log_range(h, first_round, count); }
+int cmpc_lin_rounds_log_read(cmpc_lin_rounds* h, int first_round, int count, const cmpc_rounds_log* o) {
     return log_read(h, first_round, count, o);
 }
 

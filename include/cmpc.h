@@ -53,7 +53,8 @@ extern "C" {
                                 CMPC_FLAG_CERTIFY, cmpc_mpc_cert, cmpc_mpc_certify[_dev];
                                 CMPC_FLAG_CERTIFY_ROWS, cmpc_mpc_cert_rows, cmpc_mpc_certify_rows[_dev];
                                 CMPC_FLAG_LPV, CMPC_FLAG_LPV_AUTO, cmpc_mpc_lpv_level[_dev];
-                                CMPC_FLAG_LPV_SPLIT, cmpc_mpc_lpv_split_dev */
+                                CMPC_FLAG_LPV_SPLIT, cmpc_mpc_lpv_split_dev;
+                                cmpc_lin_build_dev, cmpc_lin_advance_dev, cmpc_lin_round_dev, cmpc_lin_rounds_* */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -783,7 +784,7 @@ typedef struct cmpc_di_rounds cmpc_di_rounds;
 
 #define CMPC_ROUNDS_LPT 8   /* from the second round on, cmpc_opts.order = cmpc_order_by_iters_dev of the previous
                                round's iteration counts (the first round: NULL, identity).  Only when an agent
-                               runs changes, never what it returns.  cmpc_di_rounds only */
+                               runs changes, never what it returns.  cmpc_di_rounds and cmpc_lin_rounds */
 
 typedef struct {
     int n_total, batch, self_offset;  /* as cmpc_lpv_rounds_dims */
@@ -897,6 +898,124 @@ int cmpc_lpv_rounds_log_read(cmpc_lpv_rounds* h, int first_round, int count, con
 int cmpc_di_rounds_log_enable(cmpc_di_rounds* h, int capacity, int flags);
 int cmpc_di_rounds_log_range(cmpc_di_rounds* h, int* first_round, int* count);
 int cmpc_di_rounds_log_read(cmpc_di_rounds* h, int first_round, int count, const cmpc_rounds_log* host_out);
+
+/* ------------------------------------------------------------------------
+ * Consensus rounds for any linear agent model: the third family.  An agent is given by its own A_k, B_k
+ * (cmpc_mpc_data, any structured linear time-varying model cmpc_solve_mpc_batch_dev takes), its own stage rows
+ * C_own / h_own (mo per stage), its own linear cost qlin_own and the two state columns ix, iy that hold its
+ * position.  Per round the builder appends the nb collision rows (compute_plane.py:41-68) and adds the coverage
+ * term (misc.py:10-18) from the exchanged trajectories; the advance applies the round update of
+ * LPV_HP_N_main.py:106-117.  DEVICE pointers, stream-ordered, no host synchronisation, no scratch,
+ * graph-capturable.  The double-integrator family above is the special case ix, iy = 0, 1, mo = 4 with its four
+ * constant rows and two constant cost entries in the caller's arrays (cmpc.scenarios.lin_of_di), bit for bit.
+ *
+ * cmpc_lin_build_dev: the rule.  Every expression is rounded as written (no fma: the bits of numpy;
+ * cmpc.scenarios.lin_rows is its numpy statement).  For local agent b (global index g = self_offset + b), with
+ * own = traj_all[g] (traj_all: n_total x (N+1) x 2) and mc = mo + nb:
+ *   qlin[b,k,:] = qlin_own[b,k,:]                                            k = 0..N
+ *   stage k = 1..N, written at row index k-1 of C (batch x N x mc x nx) and h (batch x N x mc):
+ *     rows r < mo:   C[b,k-1,r,:] = C_own[b,k-1,r,:],  h[b,k-1,r] = h_own[b,k-1,r]
+ *     row mo + i, neighbour i < nb, j = nbr[b,i]:
+ *       e = own[k-1], n = traj_all[j,k-1];  dx = n_x - e_x, dy = n_y - e_y;  nrm = sqrt(dx*dx + dy*dy)
+ *       ax = dx/nrm, ay = dy/nrm;  bb = -0.5*(ax*(e_x + n_x) + ay*(e_y + n_y))
+ *       C[b,k-1,mo+i,:] = 0 except [ix] = ax, [iy] = ay;  h[b,k-1,mo+i] = -min_dist/2 - bb
+ *     coverage, from row k:  qx = own[k]_x - traj_all[j,k]_x, qy likewise;
+ *       wgt = (2*min_dist - sqrt(qx*qx + qy*qy))/nb;  px = px + wq*wgt*ax, py = py + wq*wgt*ay, accumulated
+ *       from 0.0 in neighbour order;  then qlin[b,k,ix] += px, qlin[b,k,iy] += py
+ *   stage 0 gets no coverage term.
+ * A neighbour on the agent's own point (nrm = 0) gives NaN rows and a NaN cost at that stage, for that agent
+ * only, as in both other families: keep j != g and distinct positions (cmpc_nbr_select_dev never returns g).
+ * One workgroup per agent: the copies with consecutive lanes on consecutive addresses, the planes one lane per
+ * stage.  nbr: batch x nb global indices (may be NULL when nb == 0), not range-checked on the device.
+ *
+ * cmpc_lin_advance_dev: from z (batch x nz, reference layout, nxe = nx + ns, nz = nxe(N+1) + 2 nu N):
+ *   x0[b,:] <- z[b, nxe .. nxe+nx),  u_prev[b,:] <- z[b, nxe(N+1) .. +nu),
+ *   traj_local[b,k,:] <- (z[b, k nxe + ix], z[b, k nxe + iy]),  k = 0..N.
+ * An agent whose z holds any non-finite value is not advanced: its x0, u_prev and traj_local rows stay as they
+ * were (cmpc_lpv_advance_dev's rule), so no NaN reaches a neighbour.
+ *
+ * cmpc_lin_round_dev: cmpc_lin_build_dev into data->qlin / C / h (written despite the const, as
+ * cmpc_di_solve_dev), cmpc_solve_mpc_batch_dev(mpc_dims, w, data, out, opts), cmpc_lin_advance_dev(z = out->z,
+ * x0 = data->x0, u_prev = data->u_prev: written despite the const).  Every solver flag means what it means on
+ * cmpc_solve_mpc_batch_dev (rescue, polish, certify, the LPV flags, order, stamps; CMPC_FLAG_LPV_AUTO stays
+ * CMPC_ERR_ARG); solver errors come back unchanged.  traj_all is only read (the Jacobi round); the exchange
+ * traj_local -> traj_all is the caller's next step, and traj_local must not alias traj_all.
+ *
+ * CMPC_ERR_ARG: a NULL struct or required pointer (C_own / h_own may be NULL when mo == 0, nbr when nb == 0);
+ * ix == iy, or either outside [0, nx); nb < 0, mo < 0 or mo + nb > CMPC_MAX_MC; nx outside 1..CMPC_MAX_NX;
+ * N < 1, batch < 0 or self_offset < 0; the advance: ns outside 0..CMPC_MAX_NS, nu outside 1..CMPC_MAX_NU; the
+ * round: mpc_dims not describing the same agents (nx, N, batch not equal, or mc != mo + nb).  batch == 0:
+ * CMPC_OK without a launch.
+ * ---------------------------------------------------------------------- */
+typedef struct { int ix, iy; double min_dist, wq; } cmpc_lin_params;      /* position = state columns ix, iy */
+typedef struct { int batch, N, nb, self_offset; int nx, mo; } cmpc_lin_dims; /* mo own rows per stage; mc = mo + nb */
+typedef struct {            /* DEVICE pointers, per agent, batch-major, only read */
+    const double* qlin_own; /* batch x (N+1) x nx */
+    const double* C_own;    /* batch x N x mo x nx  (may be NULL when mo == 0) */
+    const double* h_own;    /* batch x N x mo       (may be NULL when mo == 0) */
+} cmpc_lin_own;
+
+int cmpc_lin_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* dims,
+                       const int* nbr /* batch x nb, global agent indices */, const cmpc_lin_own* own,
+                       const double* traj_all /* n_total x (N+1) x 2 */, double* qlin /* batch x (N+1) x nx */,
+                       double* C /* batch x N x (mo+nb) x nx */, double* h /* batch x N x (mo+nb) */,
+                       void* hip_stream);
+int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* dims, int ns, int nu,
+                         const double* z /* batch x nz */, double* x0 /* batch x nx */,
+                         double* u_prev /* batch x nu */, double* traj_local /* batch x (N+1) x 2 */,
+                         void* hip_stream);
+int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* ldims, const int* nbr,
+                       const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* mpc_dims,
+                       const cmpc_mpc_weights* w, const cmpc_mpc_data* data, const cmpc_mpc_out* out,
+                       const cmpc_opts* opts, double* traj_local /* batch x (N+1) x 2 */, void* hip_stream);
+
+/* The round handle of the family, built as cmpc_di_rounds is (sharding, exchange, history ring, log: see
+ * there).  A round, on the context's stream:
+ *   1. CMPC_ROUNDS_RESELECT and nb > 0: cmpc_nbr_select_dev, window (0, 0), into the handle's table;
+ *   2. cmpc_lin_round_dev on the handle's buffers; with CMPC_ROUNDS_LPT, from the second round on,
+ *      cmpc_opts.order = the handle's order buffer;
+ *   3. CMPC_ROUNDS_LPT: cmpc_order_by_iters_dev of this round's iteration counts into the order buffer;
+ *   4. the exchange (a device copy, the context's communicator, or the host's: CMPC_ROUNDS_HOST_EXCHANGE);
+ *   5. with the log on, the log row: nx, nu, ns of the handle's dims, look_col = ix.
+ * No halt rule (CMPC_ROUNDS_NO_HALT is accepted and has no effect).  A, B, qlin_own, C_own, h_own are uploaded
+ * once and never changed by the handle (CMPC_FLAG_LTI is set when A and B pass cmpc_di_rounds_create's test).
+ * opts->flags go to the solver unchanged; opts->stamps and opts->order are ignored.  _set_state replaces the
+ * predicted state of the next round by a measured one (HOST pointers, batch x nx / batch x nu; either may be
+ * NULL: that part stays).  _read, _history, _get_traj, _set_traj, _destroy and the log functions are
+ * cmpc_di_rounds_*'s.
+ * CMPC_ERR_ARG at create: what cmpc_di_rounds_create lists (its `dim` and `4 + nb` rules replaced by the
+ * dimension rules of cmpc_lin_build_dev / _advance_dev above; init->C_own / h_own may be NULL when mo == 0).
+ * CMPC_ROUNDS_RESELECT keeps cmpc_nbr_select_dev's nb <= CMPC_MAX_MC - 4. */
+typedef struct cmpc_lin_rounds cmpc_lin_rounds;
+typedef struct { int n_total, batch, self_offset, N, nb, flags, history; int nx, nu, ns, mo; } cmpc_lin_rounds_dims;
+typedef struct {    /* HOST pointers, this rank's agents, copied at create */
+    const double *A, *B;        /* batch x N x nx x nx, batch x N x nx x nu */
+    const double *x0, *u_prev;  /* batch x nx, batch x nu */
+    const double *qlin_own, *C_own, *h_own;   /* as cmpc_lin_own */
+    const int* nbr;             /* batch x nb global indices (checked: 0 <= j < n_total) */
+    const double* traj;         /* n_total x (N+1) x 2 initial exchange buffer (required) */
+} cmpc_lin_rounds_init;
+typedef struct {    /* HOST pointers, any may be NULL: the latest round of this rank's agents */
+    double *z, *kkt;            /* batch x nz (nz = (nx + ns)(N+1) + 2 nu N), batch */
+    int *iters, *status;        /* batch */
+    double *x0, *u_prev;        /* batch x nx, batch x nu: the next round's initial state and previous input */
+    int* nbr;                   /* batch x nb: the table the latest round used */
+} cmpc_lin_rounds_out;
+
+/* w: ns slacks and mc = mo + nb rows, copied at create. */
+int cmpc_lin_rounds_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights* w,
+                           const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_init* init, const cmpc_opts* opts,
+                           cmpc_lin_rounds** out);
+int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done);
+int cmpc_lin_rounds_read(cmpc_lin_rounds* h, const cmpc_lin_rounds_out* host_out);
+int cmpc_lin_rounds_history(cmpc_lin_rounds* h, int first_round, int count, double* kkt, int* iters, int* status);
+int cmpc_lin_rounds_get_traj(cmpc_lin_rounds* h, double* traj_local);
+int cmpc_lin_rounds_set_traj(cmpc_lin_rounds* h, const double* traj_all);
+int cmpc_lin_rounds_set_state(cmpc_lin_rounds* h, const double* x0, const double* u_prev);
+int cmpc_lin_rounds_destroy(cmpc_lin_rounds* h);
+int cmpc_lin_rounds_log_enable(cmpc_lin_rounds* h, int capacity, int flags);
+int cmpc_lin_rounds_log_range(cmpc_lin_rounds* h, int* first_round, int* count);
+int cmpc_lin_rounds_log_read(cmpc_lin_rounds* h, int first_round, int count, const cmpc_rounds_log* host_out);
 
 
 /* ------------------------------------------------------------------------
