@@ -39,7 +39,7 @@ __host__ __device__ constexpr int slk(int r) { return r == 0 ? -1 : (r == 1 ? 0 
 __host__ __device__ constexpr double sgn(int r) { return r < 4 ? 1.0 : -1.0; }
 
 struct Lds3 {
-    int cst, A, B, C, H, Pq, x0, up, W, Gb, Yb, X, dX, yb, U, dU, rd, vb, thin, bU, Ld, red, stamps, Phi, Pst, total;
+    int cst, A, B, C, H, Pq, x0, up, W, Gb, Yb, X, dX, yb, U, dU, rd, vb, thin, bU, Ld, red, stamps, Phi, Pst, Gf, total;
     // two-wave mode (W2): the fields from W to stamps are each wave's private copy (wave 1's at + psz);
     // exchange areas: wave 1's K tiles (xk), the predictor's rho and vb (xr, xv), dU of the two passes
     // (xu0, xu1), flags (xf)
@@ -98,6 +98,37 @@ constexpr int kDsW = 6;
 template <int NB>
 __host__ __device__ constexpr int ds_cw() { return NB > 0 ? 2 * NB : 2; }
 
+// TF (the time-invariant instantiations' K build, tf_on): lane (c, s) = (l & 15, l >> 4) reads its MFMA fragment
+// entries where they lie instead of receiving them by a row transpose.  Two images serve it, each entry a pair
+// that one 16-byte read fetches:
+//   the table's fragment image, per column (d, ic) the pairs (g0, g1), (g2, 0), (g3, 0): rows s = 0, 1 read the
+//   first, row 2 the second, row 3 the third (tf_pair); slots d = -tf_lead .. -1 and d = N are all zero, so a
+//   tile's columns that have not begun yet (at most tf_lead stages before theirs, within the tile's own horizon
+//   segment) are read like any other, without a clamp;
+//   the stage weights' fragment image, per stage the rows (w_xx, w_xy), (w_yx, w_yy), (w_vx, 0), (w_vy, 0).
+// Row s of W_k g is then fma(c1, q1, fma(c0, q0, 0.0)) in every lane: the dense chain's two terms in rows 0, 1;
+// in rows 2, 3 its one term plus the product of the images' own two zeros, +0 whatever the table holds, and
+// fma(., ., 0.0) is never -0, so the sum is that term bit for bit.  -DCMPC_NO_TI_FRAG restores the transposing
+// stage body and its images (A/B builds).
+#ifdef CMPC_NO_TI_FRAG
+constexpr bool kTiFrag = false;
+#else
+constexpr bool kTiFrag = true;
+#endif
+// The two-tile instantiation keeps the transposing body and its images: with either body on the fragment images
+// it failed the bit comparison with the recursion at N = 15 and 16 (n = 30, 32; which neighbour count failed changed
+// with the body; tests/test_v3_ti_frag_gpu.py), as the three-tile code does at n = 45 .. 48
+// (mpc3_tiles); the cause is not found.
+template <bool TI, int T>
+__host__ __device__ constexpr bool tf_on() { return TI && kTiFrag && T != 2; }
+constexpr int kTfW = 8;  // doubles per stage of the weights' fragment image
+constexpr int kTfG = 6;  // doubles per column of the table's fragment image
+template <int NU>
+__host__ __device__ constexpr int tf_lead() { return 16 / NU - 1; }
+template <int NU>
+__host__ __device__ constexpr int tf_slot(int d, int ic) { return ((d + tf_lead<NU>()) * NU + ic) * kTfG; }
+__host__ __device__ constexpr int tf_pair(int s) { return s < 2 ? 0 : 2 * (s - 1); }
+
 // Segmented (parallel-in-time) forward simulation: the horizon's N stages split into four
 // segments [a_q, a_{q+1}), one per row of 16 lanes.  Each row runs its segment's recursion from a
 // zero state (row 0 from x_0); a two-step chain then carries the true state across the segment
@@ -129,6 +160,7 @@ __host__ __device__ inline Lds3 lds3_layout(int N) {
     // TI: the table of the condensed dynamics' columns (ti_slot) instead of the stages' B_k: the same size,
     // and one all-zero slot
     L.B = take(LS ? N * 3 * NU : (TI ? N + 1 : N) * NX * NU);
+    L.Gf = take(tf_on<TI, T>() ? tf_slot<NU>(N + 1, 0) : 0);  // TF: the table's fragment image (456 doubles at N = 30)
     L.C = take(LS ? N * ls_cw<NB>() : (DS ? N * ds_cw<NB>() : N * MC * NX));
     L.H = take(N * MC);
     L.Pq = take((N + 1) * NX);
@@ -145,7 +177,7 @@ __host__ __device__ inline Lds3 lds3_layout(int N) {
     // begun); Gb extends them only where they are smaller than that (short horizons, small NX).  At
     // NX = 9 the extra 12 KB it used to take halved the agents per CU (90 KB -> 78 KB); at cfg3 the
     // dX | yb alias makes room for the segmented recursions' transitions within 40 KB.
-    const int wsz = LS ? N * kLsW : (DS ? N * kDsW : N * NX * NX);
+    const int wsz = LS ? N * kLsW : (DS ? N * (tf_on<TI, T>() ? kTfW : kDsW) : N * NX * NX);
     L.W = take(wsz);
     L.dX = take((N + 1) * NX);
     L.yb = take((N + 1) * NX);
@@ -786,6 +818,25 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         for (int i = 0; i < NX * NX; ++i) ar[i] = sA[i];
 #pragma unroll
         for (int s = 0; s < NX; ++s) g[s] = sB[ti_slot<NX, NU>(0, ic) + s];
+        // TF: every slot's copy in the fragment image (tf_pair), the zero slot included
+        double* sGf = sm + L.Gf;
+        auto put_frag = [&](int d, bool zero) __attribute__((always_inline)) {
+            if constexpr (tf_on<TI, T>()) {
+                if (l < NU) {
+                    double* gp = sGf + tf_slot<NU>(d, ic);
+                    gp[0] = zero ? 0.0 : g[0];
+                    gp[1] = zero ? 0.0 : g[1];
+                    gp[2] = zero ? 0.0 : g[2];
+                    gp[3] = 0.0;
+                    gp[4] = zero ? 0.0 : g[3];
+                    gp[5] = 0.0;
+                }
+            }
+        };
+        put_frag(0, false);
+        put_frag(N, true);
+#pragma unroll
+        for (int d = 1; d <= tf_lead<NU>(); ++d) put_frag(-d, true);
         for (int d = 1; d < N; ++d) {
             double gn[NX];
 #pragma unroll
@@ -801,6 +852,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
 #pragma unroll
                 for (int s = 0; s < NX; ++s) sB[ti_slot<NX, NU>(d, ic) + s] = g[s];
             }
+            put_frag(d, false);
         }
         wsync();
     }
@@ -1154,13 +1206,25 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                             wyx = fma(phi * dy, dx, wyx);
                             wyy = fma(phi * dy, dy, wyy);
                         }
-                    double* wk = sW + k * kDsW;
-                    wk[0] = wxx;
-                    wk[1] = wxy;
-                    wk[2] = wyx;
-                    wk[3] = wyy;
-                    wk[4] = wvx;
-                    wk[5] = Q2[3 * NX + 3];
+                    if constexpr (tf_on<TI, T>()) {  // the fragment image: row s of W_k as a pair
+                        double* wk = sW + k * kTfW;
+                        wk[0] = wxx;
+                        wk[1] = wxy;
+                        wk[2] = wyx;
+                        wk[3] = wyy;
+                        wk[4] = wvx;
+                        wk[5] = 0.0;
+                        wk[6] = Q2[3 * NX + 3];
+                        wk[7] = 0.0;
+                    } else {
+                        double* wk = sW + k * kDsW;
+                        wk[0] = wxx;
+                        wk[1] = wxy;
+                        wk[2] = wyx;
+                        wk[3] = wyy;
+                        wk[4] = wvx;
+                        wk[5] = Q2[3 * NX + 3];
+                    }
                 } else {
                 // the stage's rows and 2Q into registers in one batch of LDS reads (read inside the
                 // loops below they were issued one dependent wait at a time)
@@ -1291,6 +1355,87 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 const int ke0 = (16 * (tau + 1) + NU) / NU - 1;
                 const int ke = ke0 < N ? ke0 : N;
                 for (int kk = kb; kk < ke; ++kk) stage(tau_c, kk);
+            });
+        } else if constexpr (tf_on<TI, T>()) {
+            // TF: lane (c, s) = (l & 15, l >> 4) forms its fragment entries of every tile in place.  Column
+            // 16 t + c = kc_t NU + ic of stage k is the table's slot k - kc_t: one pair read from the table's
+            // fragment image per tile, one from the weights' per stage (see tf_on), both a stage ahead into
+            // ping-pong registers.  Tile t joins at the first stage of segment t, k = kc_t - c / NU, inside the
+            // leading zero slots, and its address advances by a slot per stage from there; the padding columns
+            // (16 t + c >= n) stay on a zero slot (step 0).  Only the tiles the segment's MFMA set uses are
+            // read.  The fetch of stage N after the last one stays inside the image (slot N).
+            typedef double v2d __attribute__((ext_vector_type(2)));
+            static_assert(16 % NU == 0 && NX == 4, "tile columns share ic; four fragment rows");
+            const int c16 = l & 15, sr = l >> 4;
+            const int kc0 = c16 / NU, icf = c16 - kc0 * NU;
+            const char* gx = reinterpret_cast<const char*>(sm + L.Gf + icf * kTfG + tf_pair(sr));
+            const double* wx = sW + 2 * sr;
+            const bool odd1 = sr == 1;  // row 1's own component is the pair's second
+            constexpr int kSlotB = NU * kTfG * (int)sizeof(double);
+            const char* ap[T];
+            int step[T];
+#pragma unroll
+            for (int t2 = 0; t2 < T; ++t2) {
+                ap[t2] = gx;
+                step[t2] = 16 * t2 + c16 < n ? kSlotB : 0;
+            }
+            v2d p0[T], p1[T], w0, w1;
+            auto ld2 = [&](const void* a) __attribute__((always_inline)) { return *reinterpret_cast<const v2d*>(a); };
+            // tile tau joins: its entries of segment tau's first stage
+            auto fetch_own = [&](auto tau_c, v2d* pv) __attribute__((always_inline)) {
+                constexpr int tau = decltype(tau_c)::value;
+                ap[tau] = gx + (step[tau] != 0 ? (tf_lead<NU>() - kc0) * kSlotB : 0);
+                pv[tau] = ld2(ap[tau]);
+            };
+            // every tile of segment tau one stage on, and W_kk of that stage
+            auto fetch = [&](auto tau_c, int kk, v2d* pv, v2d& wv2) __attribute__((always_inline)) {
+                constexpr int tau = decltype(tau_c)::value;
+                static_for<0, tau + 1>([&](auto t_c) __attribute__((always_inline)) {
+                    constexpr int t2 = decltype(t_c)::value;
+                    ap[t2] += step[t2];
+                    pv[t2] = ld2(ap[t2]);
+                });
+                wv2 = ld2(wx + (kk < N ? kk : N - 1) * kTfW);
+            };
+            auto stage = [&](auto tau_c, const v2d* pv, const v2d& wv2, auto pf) __attribute__((always_inline)) {
+                constexpr int tau = decltype(tau_c)::value;
+                pf();
+                __builtin_amdgcn_sched_barrier(0);
+                double gf[tau + 1], yf[tau + 1];
+                static_for<0, tau + 1>([&](auto t_c) __attribute__((always_inline)) {
+                    constexpr int t2 = decltype(t_c)::value;
+                    const double q0 = pv[t2][0], q1 = pv[t2][1];
+                    gf[t2] = odd1 ? q1 : q0;
+                    yf[t2] = fma(wv2[1], q1, fma(wv2[0], q0, 0.0));
+                });
+                static_for<0, tau + 1>([&](auto ti_c) __attribute__((always_inline)) {
+                    constexpr int ti = decltype(ti_c)::value;
+                    static_for<0, ti + 1>([&](auto tj_c) __attribute__((always_inline)) {
+                        constexpr int tj = decltype(tj_c)::value;
+                        acc[ti * (ti + 1) / 2 + tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                            gf[ti], yf[tj], acc[ti * (ti + 1) / 2 + tj], 0, 0, 0);
+                    });
+                });
+            };
+            w0 = ld2(wx);
+            static_for<0, T>([&](auto tau_c) __attribute__((always_inline)) {
+                constexpr int tau = decltype(tau_c)::value;
+                const int kb = (16 * tau + NU) / NU - 1;
+                const int ke0 = (16 * (tau + 1) + NU) / NU - 1;
+                const int ke = ke0 < N ? ke0 : N;
+                // the previous segment's last stage fetched the tiles below: the segment's own joins them
+                fetch_own(tau_c, p0);
+                int kk = kb;
+                for (; kk + 1 < ke; kk += 2) {
+                    stage(tau_c, p0, w0, [&]() __attribute__((always_inline)) { fetch(tau_c, kk + 1, p1, w1); });
+                    stage(tau_c, p1, w1, [&]() __attribute__((always_inline)) { fetch(tau_c, kk + 2, p0, w0); });
+                }
+                if (kk < ke) {
+                    stage(tau_c, p0, w0, [&]() __attribute__((always_inline)) { fetch(tau_c, kk + 1, p1, w1); });
+#pragma unroll
+                    for (int t2 = 0; t2 <= tau; ++t2) p0[t2] = p1[t2];
+                    w0 = w1;
+                }
             });
         } else {
             // lane l carries column l of Gamma_k (Gamma_0 = 0) and of W_k Gamma_k; both reach the
