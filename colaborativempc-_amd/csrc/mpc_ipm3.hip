@@ -121,6 +121,35 @@ constexpr bool kTiFrag = true;
 // (mpc3_tiles); the cause is not found.
 template <bool TI, int T>
 __host__ __device__ constexpr bool tf_on() { return TI && kTiFrag && T != 2; }
+// Two forms of the iteration that issue less for the same operations ("iteration overhead"):
+//  inv_row_on  invert_diag takes L_q[i][c] as a row broadcast of lane i's own row of the block, fused into the
+//              fma, instead of 136 broadcast LDS reads per lane;
+//  dg_on       the K build's `+ 2R + 2D'dR D` comes from a table built once per solve (dg_slot: the iteration's
+//              own expression for every (a, bq, same / adjacent stage, last-stage factor), and one +0), the
+//              diagonal's `+ theta` from the lane that owns the input rows, which leaves the whole diagonal add
+//              (the identity on the padding) in `thin`; an element is then one index, one LDS read and one add.
+// Each performs the iteration's single-rounded operations on the same operands in the same order.
+// -DCMPC_NO_INV_ROW / -DCMPC_NO_DIAG_TAB restore the reading forms (A/B builds).
+#ifdef CMPC_NO_INV_ROW
+constexpr bool kInvRow = false;
+#else
+constexpr bool kInvRow = true;
+#endif
+#ifdef CMPC_NO_DIAG_TAB
+constexpr bool kDiagTab = false;
+#else
+constexpr bool kDiagTab = true;
+#endif
+template <int T>
+__host__ __device__ constexpr bool inv_row_on() { return kInvRow; }
+template <int T>
+__host__ __device__ constexpr bool dg_on() { return kDiagTab; }
+// table slot of (a, bq) = (row % NU, col % NU), adj: stages kr = kc +- 1 (else kr = kc), nl: kr + 1 < N; the +0
+// entry for the elements outside the band and outside the n x n block follows
+template <int NU>
+__host__ __device__ constexpr int dg_slot(int a, int bq, int adj, int nl) { return ((a * NU + bq) * 2 + adj) * 2 + nl; }
+template <int NU>
+__host__ __device__ constexpr int dg_count() { return 4 * NU * NU + 2; }
 constexpr int kTfW = 8;  // doubles per stage of the weights' fragment image
 constexpr int kTfG = 6;  // doubles per column of the table's fragment image
 template <int NU>
@@ -155,7 +184,7 @@ __host__ __device__ inline Lds3 lds3_layout(int N) {
         o += (cnt + 1) & ~1;
         return r;
     };
-    L.cst = take(NX * NX + 2 * NU * NU + 3 + 2 * NU);
+    L.cst = take(NX * NX + 2 * NU * NU + 3 + 2 * NU + (dg_on<T>() ? dg_count<NU>() : 0));  // (+ 144 B at NU = 2)
     L.A = take(LS ? N * NX * 3 : N * NX * NX);
     // TI: the table of the condensed dynamics' columns (ti_slot) instead of the stages' B_k: the same size,
     // and one all-zero slot
@@ -654,6 +683,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
     double* Qs2 = dR2 + NU * NU;      // 2Qs
     double* ub = Qs2 + 3;
     double* lb = ub + NU;
+    double* dgt = lb + NU;            // the K build's diagonal-add table (dg_on)
     double* sA = sm + L.A;
     double* sB = sm + L.B;
     double* sC = sm + L.C;
@@ -747,6 +777,19 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             R2[l] = 2.0 * c.R[l];
             dR2[l] = 2.0 * c.dR[l];
         }
+        if constexpr (dg_on<T>()) {
+            // the iteration's expression for an element off the diagonal (me = 0, and thin >= +0 there, so
+            // its product with the zero mask is the +0 written here), per dg_slot; the last entry is the +0
+            // of the elements outside the band
+            if (l < dg_count<NU>()) {
+                const int ab = l >> 2, adj = (l >> 1) & 1, nl = l & 1;
+                const int abc = ab < NU * NU ? ab : 0;
+                const double r2 = 2.0 * c.R[abc], d2 = 2.0 * c.dR[abc];
+                const double md = adj ? 0.0 : 1.0, mo = adj ? 1.0 : 0.0, f = nl ? 2.0 : 1.0;
+                const double v = fma(md, fma(d2, f, r2), fma(md * 0.0, 0.0, -mo * d2));
+                dgt[l] = ab < NU * NU ? v : 0.0;
+            }
+        }
         if (l < 3) Qs2[l] = 2.0 * c.Qs[l];
         if (l < NU) {
             ub[l] = c.u_ub[l];
@@ -758,7 +801,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             U[i] = 0.0;
             dU[i] = 0.0;
             vb[i] = 0.0;
-            thin[i] = 0.0;
+            // dg_on: the diagonal's whole add, rewritten every iteration on the rows < n: the padding's identity
+            thin[i] = (dg_on<T>() && i >= n) ? 1.0 : 0.0;
             bU[i] = 0.0;
         }
     }
@@ -1271,7 +1315,17 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 }
             } else {
 #pragma unroll
-                for (int i = 0; i < NU; ++i) thin[k * NU + i] = th[2 * i] + th[2 * i + 1];
+                for (int i = 0; i < NU; ++i) {
+                    const double thr = th[2 * i] + th[2 * i + 1];
+                    if constexpr (dg_on<T>()) {
+                        // the diagonal element's add (md = me = 1, mo = 0), once per row instead of in
+                        // every lane of the diagonal tiles
+                        const double r2 = R2[i * NU + i], d2 = dR2[i * NU + i], f = (k + 1 < N) ? 2.0 : 1.0;
+                        thin[k * NU + i] = fma(1.0, fma(d2, f, r2), fma(1.0, thr, -0.0 * d2));
+                    } else {
+                        thin[k * NU + i] = thr;
+                    }
+                }
             }
         }
         wsync();
@@ -1279,6 +1333,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         // zero the accumulators with an MFMA so they are defined in the accumulator registers:
         // a VALU zero made the tiles first touched in a late horizon segment live in VGPRs and
         // cost a VGPR<->AGPR copy (and an MFMA-result stall) per stage
+        // (Letting each segment's first stage take C = 0 instead removes the copies of the merged zero tile,
+        // 96 v_accvgpr_mov in the listing, but the peeled stage bodies cost as much: measured no gain)
         {
             const v4d z4 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -1606,6 +1662,48 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         // + 2R + 2D'dR D (block tridiagonal) + input-row curvature; identity on the padding.
         // The band half-width 2NU - 1 < 16 touches only the diagonal and first sub-diagonal tiles;
         // branch-free: unconditional (clamped) LDS reads and selects.
+        if constexpr (dg_on<T>()) {
+            // one read per element: the table's entry of (a, bq, same / adjacent stage, last stage), its +0
+            // outside the band and the n x n block (added as before: a -0 accumulator ends +0), on the
+            // diagonal the row's whole add from `thin` (the identity on the padding)
+            // Where NU divides 4 the tile and register offsets are whole stages, so (a, bq), the lane's stage
+            // difference and with it same / adjacent are the lane's own; elements whose stage difference
+            // cannot come within the band add the +0 without a read.  Only the last two tiles can reach
+            // row n or stage N - 1 (n > 16 (T - 2), mpc3_tiles); the tiles before them skip both tests
+            const int zero_at = dg_slot<NU>(NU, 0, 0, 0);
+            const int ur = l >> 4, uc = l & 15;
+            static_for<0, T>([&](auto ti_c) __attribute__((always_inline)) {
+                constexpr int ti = decltype(ti_c)::value;
+                static_for<(ti > 0 ? ti - 1 : 0), ti + 1>([&](auto tj_c) __attribute__((always_inline)) {
+                    constexpr int tj = decltype(tj_c)::value;
+                    static_for<0, 4>([&](auto r_c) __attribute__((always_inline)) {
+                        constexpr int r = decltype(r_c)::value;
+                        constexpr int ro = ti * 16 + 4 * r, co = tj * 16;
+                        constexpr bool tail = ti >= T - 2, whole = 4 % NU == 0;
+                        constexpr int q = ti * (ti + 1) / 2 + tj;
+                        if constexpr (whole && (ro - co) / NU - 15 / NU > 1) {
+                            acc[q][r] += 0.0;
+                        } else {
+                            const int row = ro + ur, col = co + uc;
+                            const int kr = whole ? ro / NU + ur / NU : row / NU;
+                            const int kc = whole ? co / NU + uc / NU : col / NU;
+                            const int a = whole ? ur % NU : row - kr * NU, bq = whole ? uc % NU : col - kc * NU;
+                            const unsigned dk1 = (unsigned)(kr - kc + 1);  // 0, 2: adjacent stages; 1: the same
+                            bool band = dk1 <= 2u;
+                            int nl = 1;
+                            if constexpr (tail) {
+                                band = band && row < n && col < n;
+                                nl = kr + 1 < N ? 1 : 0;
+                            }
+                            const int slot = dg_slot<NU>(a, bq, (int)(~dk1 & 1u), nl);
+                            const double* src = dgt + (band ? slot : zero_at);
+                            if constexpr (ti == tj) src = (row == col) ? thin + row : src;
+                            acc[q][r] += *src;
+                        }
+                    });
+                });
+            });
+        } else {
 #pragma unroll
         for (int ti = 0; ti < T; ++ti)
 #pragma unroll
@@ -1625,6 +1723,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                     add = in ? add : me;
                     acc[ti * (ti + 1) / 2 + tj][r] += add;
                 }
+        }
         STAMP(5);
 
         // ================= blocked Cholesky in the accumulator registers =================
@@ -1637,6 +1736,29 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             const int q = l >> 4, j = l & 15;
             double* Lq = Ld + (q < T ? q : 0) * 272;
             double x[16];
+            if constexpr (inv_row_on<T>()) {
+                // L_q[i][c] is entry c of lane i's own row of the block (the triangular solves' Lr pattern),
+                // fused into the fma as a row broadcast: 16 LDS reads instead of 136 broadcast reads and
+                // the registers that held them.  The same fma on the same operands, the chains in order
+                double Lw[16];
+#pragma unroll
+                for (int c4 = 0; c4 < 16; c4 += 4) {
+                    const double* Lj = Lq + j * 17 + c4;
+                    const v4d w4 = dpp_settled(v4d{Lj[0], Lj[1], Lj[2], Lj[3]});
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) Lw[c4 + e] = w4[e];
+                }
+                static_for<0, 16>([&](auto i_c) __attribute__((always_inline)) {
+                    constexpr int i = decltype(i_c)::value;
+                    double s0 = (j == i) ? 1.0 : 0.0, s1 = 0.0;
+                    static_for<0, i>([&](auto c_c) __attribute__((always_inline)) {
+                        constexpr int c = decltype(c_c)::value;
+                        if constexpr (c & 1) s1 = fnma_bcast16s<i>(x[c], Lw[c], s1);
+                        else s0 = fnma_bcast16s<i>(x[c], Lw[c], s0);
+                    });
+                    x[i] = (s0 + s1) * rcp_d(bcast16<i>(Lw[i]));
+                });
+            } else {
             static_for<0, 16>([&](auto i_c) __attribute__((always_inline)) {
                 constexpr int i = decltype(i_c)::value;
                 double s0 = (j == i) ? 1.0 : 0.0, s1 = 0.0;
@@ -1647,6 +1769,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 }
                 x[i] = (s0 + s1) * rcp_d(Lq[i * 17 + i]);
             });
+            }
             wsync();
             if (q < T) {
 #pragma unroll
