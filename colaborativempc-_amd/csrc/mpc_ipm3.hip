@@ -144,12 +144,60 @@ template <int T>
 __host__ __device__ constexpr bool inv_row_on() { return kInvRow; }
 template <int T>
 __host__ __device__ constexpr bool dg_on() { return kDiagTab; }
+//  theta_once  1 / t_r, theta and 1 / D_sigma (nine IEEE divisions) are formed once per iteration and held across
+//              the K build and the Cholesky, where the instantiation holds them without scratch (the second
+//              evaluation after the factorisation gave the first one's bits).  The two-wave mode keeps both:
+//              its wave 1 evaluates them for the predictor's right-hand side while wave 0 factors.  The two-tile
+//              instantiations keep both as well (see dg_addr_on).
+// -DCMPC_NO_THETA_ONCE restores the second evaluation (A/B builds).
+#ifdef CMPC_NO_THETA_ONCE
+constexpr bool kThetaOnce = false;
+#else
+constexpr bool kThetaOnce = true;
+#endif
+template <int T, int NX, bool W2>
+__host__ __device__ constexpr bool theta_once() { return kThetaOnce && !W2 && T != 2; }
 // table slot of (a, bq) = (row % NU, col % NU), adj: stages kr = kc +- 1 (else kr = kc), nl: kr + 1 < N; the +0
 // entry for the elements outside the band and outside the n x n block follows
 template <int NU>
 __host__ __device__ constexpr int dg_slot(int a, int bq, int adj, int nl) { return ((a * NU + bq) * 2 + adj) * 2 + nl; }
 template <int NU>
 __host__ __device__ constexpr int dg_count() { return 4 * NU * NU + 2; }
+// whether the add's element (tile (ti, tj), register r) reads at all: where NU divides 4, an element whose stage
+// difference cannot come within the band adds the +0 without a read
+template <int NU>
+__host__ __device__ constexpr bool dg_reads(int ti, int tj, int r) {
+    return !(4 % NU == 0 && (ti * 16 + 4 * r - tj * 16) / NU - 15 / NU > 1);
+}
+// ordinal of a reading element in the add's order (diagonal and first sub-diagonal tiles, registers 0..3);
+// (T, 0, 0): their count
+template <int T, int NU>
+__host__ __device__ constexpr int dg_ord(int ti, int tj, int r) {
+    int o = 0;
+    for (int i = 0; i < T; ++i)
+        for (int j = (i > 0 ? i - 1 : 0); j <= i; ++j)
+            for (int q = 0; q < 4; ++q) {
+                if (i == ti && j == tj && q == r) return o;
+                o += dg_reads<NU>(i, j, q) ? 1 : 0;
+            }
+    return o;
+}
+//  dg_addr_on  ... and the index is formed once per solve instead of in every iteration (the opaque lane index
+//              keeps it from being hoisted): the lane holds its elements' indices in the LDS image, two per
+//              dword, across the loop, and an element is an unpack, one LDS read and one add, with no
+//              compare, select or EXEC region.  -DCMPC_NO_DIAG_ADDR restores the per-iteration index.
+// Neither form is in the two-tile instantiations, which compile to the instruction stream they had before both:
+// with either, the fused round at N = 16 left build-then-solve after the second iteration (the first equal; one
+// and two neighbour rows, max |dz| 0.072 on every agent; which of the two rows failed changed with the forms
+// compiled in, N = 9 and every other tile count stayed equal): the signature of the two-tile defect that tf_on
+// records, whose cause is not found (tests/test_v3_overhead2_gpu.py).
+#ifdef CMPC_NO_DIAG_ADDR
+constexpr bool kDiagAddr = false;
+#else
+constexpr bool kDiagAddr = true;
+#endif
+template <int T, int NX, int NU>
+__host__ __device__ constexpr bool dg_addr_on() { return kDiagAddr && dg_on<T>() && T != 2; }
 constexpr int kTfW = 8;  // doubles per stage of the weights' fragment image
 constexpr int kTfG = 6;  // doubles per column of the table's fragment image
 template <int NU>
@@ -979,6 +1027,54 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
     // and the slack directions multiply by it)
     double iDs[NS] = {1.0, 1.0, 1.0}, rsig[NS] = {0.0, 0.0, 0.0}, dsg[NS] = {0.0, 0.0, 0.0};
     v4d acc[NT];
+    // dg_on: where lane lv's element (tile (ti, tj), register r) of the K build's diagonal add lies: the table's
+    // entry of (a, bq, same / adjacent stage, last stage), its +0 outside the band and the n x n block, on the
+    // diagonal the row's whole add in `thin`.  Where NU divides 4 the tile and register offsets are whole stages,
+    // so (a, bq), the lane's stage difference and with it same / adjacent are the lane's own.  Only the last two
+    // tiles can reach row n or stage N - 1 (n > 16 (T - 2), mpc3_tiles); the tiles before them skip both tests
+    auto dg_src = [&](auto ti_c, auto tj_c, auto r_c, int lv) __attribute__((always_inline)) -> const double* {
+        constexpr int ti = decltype(ti_c)::value, tj = decltype(tj_c)::value, r = decltype(r_c)::value;
+        constexpr int ro = ti * 16 + 4 * r, co = tj * 16;
+        constexpr bool tail = ti >= T - 2, whole = 4 % NU == 0;
+        const int zero_at = dg_slot<NU>(NU, 0, 0, 0);
+        const int ur = lv >> 4, uc = lv & 15;
+        const int row = ro + ur, col = co + uc;
+        const int kr = whole ? ro / NU + ur / NU : row / NU;
+        const int kc = whole ? co / NU + uc / NU : col / NU;
+        const int a = whole ? ur % NU : row - kr * NU, bq = whole ? uc % NU : col - kc * NU;
+        const unsigned dk1 = (unsigned)(kr - kc + 1);  // 0, 2: adjacent stages; 1: the same
+        bool band = dk1 <= 2u;
+        int nl = 1;
+        if constexpr (tail) {
+            band = band && row < n && col < n;
+            nl = kr + 1 < N ? 1 : 0;
+        }
+        const int slot = dg_slot<NU>(a, bq, (int)(~dk1 & 1u), nl);
+        const double* src = dgt + (band ? slot : zero_at);
+        if constexpr (ti == tj) src = (row == col) ? thin + row : src;
+        return src;
+    };
+    // dg_addr_on: the reading elements' indices in the LDS image (below 2^16 doubles: the whole LDS is), two per
+    // dword, formed here once and held across the loop
+    constexpr int DGN = dg_addr_on<T, NX, NU>() ? dg_ord<T, NU>(T, 0, 0) : 0;
+    unsigned dgo[DGN > 0 ? (DGN + 1) / 2 : 1];
+    if constexpr (DGN > 0) {
+#pragma unroll
+        for (int i = 0; i < (DGN + 1) / 2; ++i) dgo[i] = 0u;
+        static_for<0, T>([&](auto ti_c) __attribute__((always_inline)) {
+            constexpr int ti = decltype(ti_c)::value;
+            static_for<(ti > 0 ? ti - 1 : 0), ti + 1>([&](auto tj_c) __attribute__((always_inline)) {
+                constexpr int tj = decltype(tj_c)::value;
+                static_for<0, 4>([&](auto r_c) __attribute__((always_inline)) {
+                    constexpr int r = decltype(r_c)::value;
+                    if constexpr (dg_reads<NU>(ti, tj, r)) {
+                        constexpr int o = dg_ord<T, NU>(ti, tj, r);
+                        dgo[o >> 1] |= (unsigned)(dg_src(ti_c, tj_c, r_c, l) - sm) << (16 * (o & 1));
+                    }
+                });
+            });
+        });
+    }
     double alpha_prev = 1;  // step of the previous iteration (kShortStep guard)
     for (it = 1; it <= c.max_iter; ++it) {
         // Opaque zero: the lane-index arithmetic and lane masks below are recomputed inside the
@@ -1154,9 +1250,11 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
 
         // ================= Newton matrix K = Gamma' W Gamma + Hc + diag =================
         // theta = lam / t through 1 / t_r, and 1 / D_sigma.  The passes need 1 / t_r, theta and 1 / D_sigma
-        // again: they recompute them after the factorisation, bit for bit, rather than hold 15 doubles
-        // in registers across the K build and the Cholesky (held, they made the T = 4 instantiation
-        // spill to scratch).  `oz` is an opaque zero that keeps the compiler from merging the two.
+        // again.  theta_once: the 15 doubles stay in registers across the K build and the Cholesky (with the
+        // accumulator registers at 254 they made the T = 4 instantiation spill; since the iteration-overhead
+        // pass no instantiation does).  Otherwise (the two-wave mode, -DCMPC_NO_THETA_ONCE) the passes
+        // recompute them after the factorisation, bit for bit; `oz` is an opaque zero that keeps the
+        // compiler from merging the two.
         double tin[RX];
         auto theta = [&](double oz) __attribute__((always_inline)) {
 #pragma unroll
@@ -1662,7 +1760,28 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         // + 2R + 2D'dR D (block tridiagonal) + input-row curvature; identity on the padding.
         // The band half-width 2NU - 1 < 16 touches only the diagonal and first sub-diagonal tiles;
         // branch-free: unconditional (clamped) LDS reads and selects.
-        if constexpr (dg_on<T>()) {
+        if constexpr (DGN > 0) {
+            // dg_addr_on: where each element lies depends on the lane, n and N alone; the lane formed the
+            // indices once per solve (dgo, before the loop), so an element is an unpack, a read and the add
+            // (the elements that cannot come within the band add the +0 without a read, as below)
+            static_for<0, T>([&](auto ti_c) __attribute__((always_inline)) {
+                constexpr int ti = decltype(ti_c)::value;
+                static_for<(ti > 0 ? ti - 1 : 0), ti + 1>([&](auto tj_c) __attribute__((always_inline)) {
+                    constexpr int tj = decltype(tj_c)::value;
+                    static_for<0, 4>([&](auto r_c) __attribute__((always_inline)) {
+                        constexpr int r = decltype(r_c)::value;
+                        constexpr int q = ti * (ti + 1) / 2 + tj;
+                        if constexpr (!dg_reads<NU>(ti, tj, r)) {
+                            acc[q][r] += 0.0;
+                        } else {
+                            constexpr int o = dg_ord<T, NU>(ti, tj, r);
+                            const unsigned w = dgo[o >> 1];
+                            acc[q][r] += sm[(o & 1) ? w >> 16 : w & 0xffffu];
+                        }
+                    });
+                });
+            });
+        } else if constexpr (dg_on<T>()) {
             // one read per element: the table's entry of (a, bq, same / adjacent stage, last stage), its +0
             // outside the band and the n x n block (added as before: a -0 accumulator ends +0), on the
             // diagonal the row's whole add from `thin` (the identity on the padding)
@@ -1979,10 +2098,12 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         if (wvi == 0) invert_diag();  // (W2: after the hand-over; before it, its registers spilled)
         // this lane's diagonal block (J = lane >> 4) of L^{-1}: row / column (l & 15)
         const double* Lme = Ld + ((l >> 4) < T ? (l >> 4) : 0) * 272;
-        if (wvi == 0) {
-            int ozi;
-            asm volatile("v_mov_b32 %0, 0" : "=v"(ozi));
-            theta((double)ozi);
+        if constexpr (!theta_once<T, NX, W2>()) {
+            if (wvi == 0) {
+                int ozi;
+                asm volatile("v_mov_b32 %0, 0" : "=v"(ozi));
+                theta((double)ozi);
+            }
         }
         for (int pass = 0; pass < 2; ++pass) {
             if (!W2 || !kW2Rhs || pass) {
