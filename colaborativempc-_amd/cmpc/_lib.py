@@ -221,6 +221,23 @@ class cmpc_lin_rounds_out(ct.Structure):
     _fields_ = [("z", _DP), ("kkt", _DP), ("iters", _IP), ("status", _IP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP)]
 
 
+CMPC_TABLE_HOLD = 0        # a stage table past its end holds its last stage
+CMPC_TABLE_PERIODIC = 1    # row(tau) = tau mod T
+
+
+class cmpc_lin_table_dims(ct.Structure):
+    _fields_ = [("T", ct.c_int), ("mode", ct.c_int)]
+
+
+class cmpc_lin_table(ct.Structure):    # device pointers (cmpc_lin_rounds_table_write: host pointers)
+    _fields_ = [("A", _DP), ("B", _DP), ("qlin", _DP), ("C", _DP), ("h", _DP)]
+
+
+class cmpc_lin_rounds_table_init(ct.Structure):
+    _fields_ = [("T", ct.c_int), ("mode", ct.c_int), ("t0", ct.c_int), ("A", _DP), ("B", _DP), ("qlin", _DP),
+                ("C", _DP), ("h", _DP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP), ("traj", _DP)]
+
+
 class cmpc_log_dims(ct.Structure):
     _fields_ = [(k, ct.c_int) for k in ("batch", "nx", "nu", "ns", "N", "look_col")]
 
@@ -391,6 +408,21 @@ SIGNATURES = {
     "cmpc_lin_rounds_log_enable": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
     "cmpc_lin_rounds_log_range": (ct.c_int, [ct.c_void_p, _IP, _IP]),
     "cmpc_lin_rounds_log_read": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_rounds_log)]),
+    "cmpc_lin_table_build_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_lin_dims), ct.c_int,
+                                            ct.POINTER(cmpc_lin_table_dims), ct.POINTER(cmpc_lin_table), ct.c_int, _IP,
+                                            _DP, _DP, _DP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_lin_table_round_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_lin_dims), _IP,
+                                            ct.POINTER(cmpc_lin_table_dims), ct.POINTER(cmpc_lin_table), ct.c_int, _DP,
+                                            ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                            ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out), ct.POINTER(cmpc_opts),
+                                            _DP, ct.c_void_p]),
+    "cmpc_lin_rounds_create_table": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_mpc_weights),
+                                                ct.POINTER(cmpc_lin_rounds_dims),
+                                                ct.POINTER(cmpc_lin_rounds_table_init), ct.POINTER(cmpc_opts),
+                                                ct.POINTER(ct.c_void_p)]),
+    "cmpc_lin_rounds_get_time": (ct.c_int, [ct.c_void_p, _IP]),
+    "cmpc_lin_rounds_set_time": (ct.c_int, [ct.c_void_p, ct.c_int]),
+    "cmpc_lin_rounds_table_write": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_lin_table)]),
 }
 
 CMPC_COMM_ID_BYTES = 128

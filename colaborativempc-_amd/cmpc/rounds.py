@@ -249,6 +249,79 @@ def lin_round_dev(prm, own, nbr, traj_all, shared, dev, out, traj_local, self_of
     del keep
 
 
+def _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream):
+    """What the two stage-table wrappers share: the shapes read off the table's tensors (A (B, T, nx, nx), B (B, T,
+    nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo); C / h None when mo = 0), cmpc_lin_dims,
+    cmpc_lin_table_dims, cmpc_lin_table."""
+    import torch
+
+    A, Bm, q, C, h = table["A"], table["B"], table["qlin"], table.get("C"), table.get("h")
+    B, T, nx = (int(v) for v in q.shape)
+    nu = int(Bm.shape[3]) if Bm.dim() == 4 else -1
+    mo = 0 if C is None else int(C.shape[2])
+    nb = 0 if nbr is None else int(nbr.shape[1])
+    if tuple(A.shape) != (B, T, nx, nx) or tuple(Bm.shape) != (B, T, nx, nu) or traj_all.dim() != 3 or \
+            tuple(traj_all.shape[1:]) != (N + 1, 2) or (mo and (tuple(C.shape) != (B, T, mo, nx) or
+                                                                 tuple(h.shape) != (B, T, mo))):
+        raise ValueError("table: A (B, T, nx, nx), B (B, T, nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo); "
+                         "traj_all (n_total, N+1, 2)")
+    ctx = ctx or L.default_context(traj_all.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(traj_all.device)
+    dims = L.cmpc_lin_dims(B, int(N), nb, int(self_offset), nx, mo)
+    tab = L.cmpc_lin_table(_tptr(A), _tptr(Bm), _tptr(q), _tptr(C) if mo else None, _tptr(h) if mo else None)
+    return ctx, dims, nu, L.cmpc_lin_table_dims(T, int(mode)), tab, (_tptr(nbr) if nb and B else None), \
+        ct.c_void_p(getattr(stream, "cuda_stream", stream))
+
+
+def lin_table_build_dev(prm, table, t, N, nbr, traj_all, mode=L.CMPC_TABLE_HOLD, self_offset=0, out=None, ctx=None,
+                        stream=None):
+    """A round's whole build for agents given by a stage table — one launch of cmpc_lin_table_build_dev on
+    ``stream`` (default: torch's current one), no host synchronisation: the A / B windows at time ``t``
+    (``scenarios.lin_window``) and ``scenarios.lin_rows`` of that window's own data, bit for bit.  ``table``: dict
+    of contiguous fp64 CUDA tensors A (B, T, nx, nx), B (B, T, nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T,
+    mo) (the last two None when mo = 0); ``nbr`` (B, nb) int32 (None when nb = 0); ``traj_all`` (n_total, N+1, 2).
+    Writes ``out`` = (A, B, qlin, C, h) (allocated when None) and returns it."""
+    import torch
+
+    ctx, dims, nu, td, tab, pn, st = _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream)
+    B, N, nx, mc = dims.batch, dims.N, dims.nx, dims.mo + dims.nb
+    shapes = ((B, N, nx, nx), (B, N, nx, nu), (B, N + 1, nx), (B, N, mc, nx), (B, N, mc))
+    if out is None:
+        out = tuple(torch.empty(shp, dtype=torch.float64, device=traj_all.device) for shp in shapes)
+    if tuple(tuple(o.shape) for o in out) != shapes:
+        raise ValueError("out: A (B, N, nx, nx), B (B, N, nx, nu), qlin (B, N+1, nx), C (B, N, mo+nb, nx), h (B, N, mo+nb)")
+    if B == 0:   # empty tensors have no address to hand over; the entry point launches nothing either
+        return out
+    # (no rows at all: C and h are empty and never written; the entry point still wants an address)
+    spare = torch.empty(1, dtype=torch.float64, device=traj_all.device) if mc == 0 else None
+    ctx.check(ctx.lib.cmpc_lin_table_build_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), nu, ct.byref(td),
+                                               ct.byref(tab), int(t), pn, _tptr(traj_all),
+                                               *[_tptr(o if o.numel() else spare) for o in out], st))
+    return out
+
+
+def lin_table_round_dev(prm, table, t, nbr, traj_all, shared, dev, out, traj_local, mode=L.CMPC_TABLE_HOLD,
+                        self_offset=0, opts=None, ctx=None, stream=None):
+    """One round of stage-table agents on the device (cmpc_lin_table_round_dev): ``lin_table_build_dev`` at time
+    ``t`` into ``dev["A" | "B" | "qlin" | "C" | "h"]``, then as ``lin_round_dev``: the solver on ``dev`` with
+    ``shared`` and ``opts``, the advance into ``dev["x0"]``, ``dev["u_prev"]`` and ``traj_local``.  Moving ``t`` on
+    and the exchange stay the caller's."""
+    from .solver import PER_AGENT
+
+    ctx, dims, nu, td, tab, pn, st = _lin_table_args(table, int(shared["N"]), nbr, traj_all, mode, self_offset, ctx,
+                                                     stream)
+    w, keep = _weights(shared)
+    data = L.cmpc_mpc_data(*[_tptr(dev[k]) for k in PER_AGENT])
+    o_ = L.cmpc_mpc_out(_tptr(out["z"]), _tptr(out.get("kkt")), _tptr(out.get("iters")), _tptr(out.get("status")))
+    ctx.check(ctx.lib.cmpc_lin_table_round_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(td),
+                                               ct.byref(tab), int(t), _tptr(traj_all),
+                                               ct.byref(_dims(shared, dims.batch)), ct.byref(w), ct.byref(data),
+                                               ct.byref(o_), None if opts is None else ct.byref(opts),
+                                               _tptr(traj_local), st))
+    del keep
+
+
 def _di_params(p):
     """cmpc_di_params of a scenario's ``params``."""
     return L.cmpc_di_params(int(p["dim"]), *(float(p[k]) for k in ("v_ref", "q_v", "q_lane", "hw", "min_vel", "max_vel",
@@ -320,10 +393,10 @@ class _RoundsHandle:
         return (L.CMPC_ROUNDS_HOST_EXCHANGE if host_exchange else 0) | (0 if halt else L.CMPC_ROUNDS_NO_HALT) | \
             (L.CMPC_ROUNDS_RESELECT if reselect else 0) | (L.CMPC_ROUNDS_LPT if lpt else 0)
 
-    def _create(self, args, log, log_separation):
-        """<prefix>create(ctx, *args, &h), then the log (``log`` = capacity)."""
+    def _create(self, args, log, log_separation, create="create"):
+        """<prefix><create>(ctx, *args, &h), then the log (``log`` = capacity)."""
         h = ct.c_void_p()
-        create = getattr(self.ctx.lib, self._fn + "create")
+        create = getattr(self.ctx.lib, self._fn + create)
         self.ctx.check(create(self.ctx.h, *[ct.byref(a) for a in args], ct.byref(h)))
         self.h = h
         self.log_separation = bool(log_separation)
@@ -810,8 +883,8 @@ class LinRoundsHandle(_RoundsHandle):
 
     _fn = "cmpc_lin_rounds_"
 
-    def __init__(self, shared, prm, own, A, B, x0, u_prev, nbr, traj, rank=0, world=1, ctx=None, opts=None,
-                 host_exchange=False, reselect=False, lpt=None, history=1, log=0, log_separation=False):
+    def _shard(self, shared, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history):
+        """The wrapper's attributes and cmpc_lin_rounds_dims; returns (this rank's slice, nbr as (n, nb) int32)."""
         n = int(np.shape(x0)[0])
         if n % world:
             raise ValueError("agents must be divisible by the number of ranks")
@@ -827,6 +900,11 @@ class LinRoundsHandle(_RoundsHandle):
         flags = self._flags(host_exchange, reselect=reselect, lpt=self.lpt)
         self.dims = L.cmpc_lin_rounds_dims(n, self.B, sl.start, self.N, self.nb, flags, int(history), self.nx, self.nu,
                                            self.ns, self.mo)
+        return sl, nbr
+
+    def __init__(self, shared, prm, own, A, B, x0, u_prev, nbr, traj, rank=0, world=1, ctx=None, opts=None,
+                 host_exchange=False, reselect=False, lpt=None, history=1, log=0, log_separation=False):
+        sl, nbr = self._shard(shared, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history)
         w, wkeep = _weights(shared)
         opt = lambda a: None if a is None or self.mo == 0 else L.f64(np.asarray(a)[sl])   # noqa: E731
         keep = [L.f64(np.asarray(A)[sl]), L.f64(np.asarray(B)[sl]), L.f64(np.asarray(x0)[sl]),
@@ -880,3 +958,65 @@ class LinRoundsHandle(_RoundsHandle):
         if (a is not None and a.shape != (self.B, self.nx)) or (b is not None and b.shape != (self.B, self.nu)):
             raise ValueError("x0: (B, nx), u_prev: (B, nu)")
         self._call("set_state", L.dptr(a), L.dptr(b))
+
+
+class LinTableRoundsHandle(LinRoundsHandle):
+    """``LinRoundsHandle`` for time-varying agents (cmpc_lin_rounds_create_table): the model, the own cost and the
+    own rows are a stage table, and round r plans with the table's window at the handle's time — stages t .. t+N,
+    ``scenarios.lin_window`` — which a round that ran moves on one stage.  ``table``: dict of population arrays
+    A (n, T, nx, nx), B (n, T, nx, nu), qlin (n, T, nx), C (n, T, mo, nx), h (n, T, mo) (C / h None when the agents
+    have no own rows); ``mode``: ``CMPC_TABLE_HOLD`` (past its end the table holds its last stage) or
+    ``CMPC_TABLE_PERIODIC``; ``t0``: the first round's time.  Everything else as ``LinRoundsHandle``."""
+
+    def __init__(self, shared, prm, table, x0, u_prev, nbr, traj, mode=L.CMPC_TABLE_HOLD, t0=0, rank=0, world=1,
+                 ctx=None, opts=None, host_exchange=False, reselect=False, lpt=None, history=1, log=0,
+                 log_separation=False):
+        from .scenarios import lin_table_rows_of
+
+        self.T, self.mode = lin_table_rows_of(table), int(mode)
+        sl, nbr = self._shard(shared, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history)
+        w, wkeep = _weights(shared)
+        opt = lambda a: None if a is None or self.mo == 0 else L.f64(np.asarray(a)[sl])   # noqa: E731
+        keep = [L.f64(np.asarray(table[k])[sl]) for k in ("A", "B", "qlin")] + \
+            [opt(table.get("C")), opt(table.get("h")), L.f64(np.asarray(x0)[sl]), L.f64(np.asarray(u_prev)[sl])]
+        knbr, ktraj = L.i32(nbr[sl]), L.f64(traj)
+        init = L.cmpc_lin_rounds_table_init(self.T, self.mode, int(t0), *[L.dptr(a) for a in keep],
+                                            L.iptr(knbr) if self.nb else None, L.dptr(ktraj))
+        self._create((_lin_params(prm), w, self.dims, init, opts if opts is not None else L.opts()), log,
+                     log_separation, create="create_table")
+
+    @classmethod
+    def of_di(cls, scen, tol=None, max_iter=None, fp32=False, T=1, **kw):
+        """The handle of a ``scenarios.DIScenario`` as a stage table of ``T`` equal rows under CMPC_TABLE_HOLD
+        (``scenarios.lin_table_of_di``): round for round what ``LinRoundsHandle.of_di(scen)`` computes."""
+        from .scenarios import lin_table_of_di
+
+        lin = lin_table_of_di(scen, T)
+        return cls(scen.shared, lin["prm"], lin["table"], scen.x0, scen.u_prev, scen.nbr, scen.traj, mode=lin["mode"],
+                   opts=_di_opts(tol, max_iter, fp32), **kw)
+
+    @property
+    def time(self):
+        """The time t of the next round: it plans with table rows row(t) .. row(t + N)."""
+        t = ct.c_int()
+        self._call("get_time", ct.byref(t))
+        return t.value
+
+    def set_time(self, t):
+        """The next round plans at time ``t`` (0 <= t < T)."""
+        self._call("set_time", int(t))
+
+    def write_table(self, first_row, A=None, B=None, qlin=None, C=None, h=None):
+        """Overwrites table rows [first_row, first_row + count) of this handle's agents: each array given is (B,
+        count, ...) in the table's shapes with ``count`` for T (the same count in every one); None: that part stays
+        as it was.  No wrap: split a write that passes the table's end.  Carrying A or B withdraws CMPC_FLAG_LTI."""
+        nx, nu, mo = self.nx, self.nu, self.mo
+        tail = dict(A=(nx, nx), B=(nx, nu), qlin=(nx,), C=(mo, nx), h=(mo,))
+        arrs = {k: L.f64(v) for k, v in dict(A=A, B=B, qlin=qlin, C=C, h=h).items() if v is not None}
+        counts = {a.shape[1] for a in arrs.values() if a.ndim >= 2}
+        if len(counts) > 1 or any(a.ndim < 2 or a.shape != (self.B, a.shape[1]) + tail[k] for k, a in arrs.items()):
+            raise ValueError("write_table: arrays (B, count, ...) in the table's shapes, one count")
+        if mo == 0:                                         # (no own rows: nothing to hand over)
+            arrs.pop("C", None), arrs.pop("h", None)
+        rows = L.cmpc_lin_table(*[L.dptr(arrs.get(k)) for k in ("A", "B", "qlin", "C", "h")])
+        self._call("table_write", int(first_row), counts.pop() if counts else 0, ct.byref(rows))

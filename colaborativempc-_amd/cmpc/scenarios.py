@@ -243,6 +243,70 @@ def lin_of_di(scen, rows=None):
                 self_offset=sl.start or 0)
 
 
+TABLE_HOLD, TABLE_PERIODIC = 0, 1   # CMPC_TABLE_HOLD, CMPC_TABLE_PERIODIC
+
+
+def lin_table_rows(T, t, n, mode=TABLE_HOLD):
+    """The stage-table rule of include/cmpc.h: the table rows of the ``n`` absolute stages t, t+1, .., t+n-1 of a
+    table of ``T`` rows — tau mod T (``TABLE_PERIODIC``) or min(tau, T-1) (``TABLE_HOLD``: past its end the table
+    holds its last stage).  Returns an (n,) int64 index vector."""
+    T, t, n, mode = int(T), int(t), int(n), int(mode)
+    if T < 1 or t < 0 or n < 0 or mode not in (TABLE_HOLD, TABLE_PERIODIC):
+        raise ValueError("lin_table_rows: T >= 1, t >= 0, n >= 0, mode TABLE_HOLD or TABLE_PERIODIC")
+    tau = t + np.arange(n, dtype=np.int64)
+    return tau % T if mode == TABLE_PERIODIC else np.minimum(tau, T - 1)
+
+
+def lin_table_rows_of(table):
+    """The number of rows T of a stage table, after checking that its arrays agree: ``table`` is dict(A (B, T, nx,
+    nx), B (B, T, nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo)), C / h None (or absent) when the
+    agents have no own rows."""
+    A, Bm, q = (np.asarray(table[k]) for k in ("A", "B", "qlin"))
+    C, h = table.get("C"), table.get("h")
+    if A.ndim != 4 or Bm.ndim != 4 or q.ndim != 3 or (C is None) != (h is None):
+        raise ValueError("table: A (B, T, nx, nx), B (B, T, nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo)")
+    n, T, nx = q.shape
+    ok = T >= 1 and A.shape == (n, T, nx, nx) and Bm.shape[:3] == (n, T, nx)
+    if C is not None:
+        C, h = np.asarray(C), np.asarray(h)
+        ok = ok and C.ndim == 4 and C.shape[:2] == (n, T) and C.shape[3] == nx and h.shape == C.shape[:3]
+    if not ok:
+        raise ValueError("table: A (B, T, nx, nx), B (B, T, nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo)")
+    return T
+
+
+def lin_window(table, t, N, mode=TABLE_HOLD):
+    """Host statement of the window of a stage table at time ``t`` (cmpc_lin_table_build_dev, include/cmpc.h):
+    A_win[b,k] = A[b,row(t+k)], B likewise (k = 0..N-1), qlin_own[b,k] = qlin[b,row(t+k)] (k = 0..N),
+    C_own[b,k-1] = C[b,row(t+k)], h_own likewise (k = 1..N); copies, bit for bit.  Returns (A (B, N, nx, nx),
+    B (B, N, nx, nu), own) with ``own`` in ``lin_rows``' form."""
+    T, N = lin_table_rows_of(table), int(N)
+    if N < 1:
+        raise ValueError("lin_window: N >= 1")
+    r = lin_table_rows(T, t, N + 1, mode)
+    C, h = table.get("C"), table.get("h")
+    own = dict(qlin_own=np.asarray(table["qlin"], np.float64)[:, r].copy(),
+               C_own=None if C is None else np.asarray(C, np.float64)[:, r[1:]].copy(),
+               h_own=None if h is None else np.asarray(h, np.float64)[:, r[1:]].copy())
+    return np.asarray(table["A"], np.float64)[:, r[:-1]].copy(), np.asarray(table["B"], np.float64)[:, r[:-1]].copy(), own
+
+
+def lin_table_of_di(scen, T=1, rows=None):
+    """A ``DIScenario`` as a stage table: ``lin_of_di``'s arrays are constant over stages, so one row under
+    ``TABLE_HOLD`` is the double integrator again (``lin_window`` at any t gives ``lin_of_di``'s arrays and the
+    scenario's A, B, bit for bit); ``T`` > 1 repeats that row.  Returns ``lin_of_di``'s dict with ``table`` =
+    dict(A, B, qlin, C, h) and ``mode`` in place of ``own``."""
+    lin = lin_of_di(scen, rows)
+    sl = slice(0, scen.n_agents) if rows is None else rows
+    if int(T) < 1 or any((np.asarray(a)[sl] != np.asarray(a)[sl][:, :1]).any() for a in (scen.A, scen.B)):
+        raise ValueError("lin_table_of_di: T >= 1, and a scenario whose A, B are the same at every stage")
+    own = lin.pop("own")
+    rep = lambda a: np.repeat(np.asarray(a, np.float64)[:, :1], int(T), axis=1)   # noqa: E731
+    lin.update(table=dict(A=rep(scen.A[sl]), B=rep(scen.B[sl]), qlin=rep(own["qlin_own"]), C=rep(own["C_own"]),
+                          h=rep(own["h_own"])), mode=TABLE_HOLD)
+    return lin
+
+
 def make_di(n_agents, N, nb=2, dim=2, seed=SEED):
     rng = np.random.default_rng(seed)
     nx, nu = 2 * dim, dim

@@ -1,6 +1,7 @@
 // C ABI of libcmpc (include/cmpc.h): context management, host<->device staging
 // and dispatch of the batched kernels.  No CPU solver exists behind this ABI:
 // without a gfx950 device every entry point fails with CMPC_ERR_DEVICE.
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -943,6 +944,34 @@ int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_l
     return CMPC_OK;
 }
 
+// What cmpc_lin_round_dev and cmpc_lin_table_round_dev check after their own rules: the two dims structs describe
+// the same agents, and every argument rule of the solver before the first launch (cmpc_solve_mpc_batch_dev
+// repeats them).
+static int lin_round_check(cmpc_ctx* ctx, const cmpc_lin_dims* d, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                           const cmpc_opts* opts) {
+    if (dims->batch != d->batch || dims->N != d->N || dims->nx != d->nx || dims->mc != d->mo + d->nb)
+        return fail(ctx, CMPC_ERR_ARG, "linear-model and solver dimensions differ");
+    cmpc::MpcConst mc;
+    const char* msg = nullptr;
+    const int rc = cmpc::mpc_prepare(dims, w, opts, &mc, &msg);
+    if (rc != CMPC_OK) return fail(ctx, rc, msg);
+    if (opts && (opts->flags & CMPC_FLAG_LPV_AUTO) && !(opts->flags & CMPC_FLAG_LPV))
+        return fail(ctx, CMPC_ERR_ARG, "CMPC_FLAG_LPV_AUTO needs a host wait, so a device-pointer entry cannot take it: "
+                                       "run cmpc_mpc_lpv_level_dev and pass CMPC_FLAG_LPV");
+    return CMPC_OK;
+}
+
+// ... and what they run after their build: the solve, then the advance into data->x0 / u_prev and traj_local
+static int lin_solve_advance(cmpc_ctx* ctx, const cmpc::LinConst& c, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+                             const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_opts* opts, double* traj_local,
+                             void* stream) {
+    const int rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream);
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(cmpc::lin_advance_launch(c, dims->ns, dims->nu, out->z, const_cast<double*>(in->x0),
+                                     const_cast<double*>(in->u_prev), traj_local, dims->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
 int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
                        const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* dims,
                        const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
@@ -954,25 +983,70 @@ int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin
     cmpc::LinConst c;
     int rc = lin_const(ctx, prm, d, &c);
     if (rc != CMPC_OK) return rc;
-    if (dims->batch != d->batch || dims->N != d->N || dims->nx != d->nx || dims->mc != d->mo + d->nb)
-        return fail(ctx, CMPC_ERR_ARG, "linear-model and solver dimensions differ");
-    // every argument rule of the solver before the first launch (cmpc_solve_mpc_batch_dev repeats them)
-    cmpc::MpcConst mc;
-    const char* msg = nullptr;
-    if ((rc = cmpc::mpc_prepare(dims, w, opts, &mc, &msg)) != CMPC_OK) return fail(ctx, rc, msg);
-    if (opts && (opts->flags & CMPC_FLAG_LPV_AUTO) && !(opts->flags & CMPC_FLAG_LPV))
-        return fail(ctx, CMPC_ERR_ARG, "CMPC_FLAG_LPV_AUTO needs a host wait, so a device-pointer entry cannot take it: "
-                                       "run cmpc_mpc_lpv_level_dev and pass CMPC_FLAG_LPV");
+    if ((rc = lin_round_check(ctx, d, dims, w, opts)) != CMPC_OK) return rc;
     if (d->batch == 0) return CMPC_OK;
     if ((rc = set_device(ctx)) != CMPC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const cmpc::LinPtrs p{nbr, own->qlin_own, own->C_own, own->h_own, traj_all, const_cast<double*>(in->qlin),
                           const_cast<double*>(in->C), const_cast<double*>(in->h)};
     HIP_TRY(cmpc::lin_build_launch(c, p, d->batch, s));
-    if ((rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream)) != CMPC_OK) return rc;
-    HIP_TRY(cmpc::lin_advance_launch(c, dims->ns, dims->nu, out->z, const_cast<double*>(in->x0),
-                                     const_cast<double*>(in->u_prev), traj_local, d->batch, s));
+    return lin_solve_advance(ctx, c, dims, w, in, out, opts, traj_local, stream);
+}
+
+// the stage-table rules of cmpc_lin_table_build_dev / _round_dev (d has passed lin_const); no device call
+static int lin_table_const(cmpc_ctx* ctx, const cmpc_lin_dims* d, int nu, const cmpc_lin_table_dims* td,
+                           const cmpc_lin_table* tab, int t, cmpc::LinTableConst* tc) {
+    if (td->T < 1 || (td->mode != CMPC_TABLE_HOLD && td->mode != CMPC_TABLE_PERIODIC))
+        return fail(ctx, CMPC_ERR_ARG, "bad stage table (T >= 1, mode CMPC_TABLE_HOLD or CMPC_TABLE_PERIODIC)");
+    if (t < 0 || t > INT_MAX - d->N) return fail(ctx, CMPC_ERR_ARG, "bad table time (0 <= t <= INT_MAX - N)");
+    if (nu < 1 || nu > CMPC_MAX_NU) return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (1 <= nu <= 4)");
+    if (!tab->A || !tab->B || !tab->qlin || (d->mo > 0 && (!tab->C || !tab->h)))
+        return fail(ctx, CMPC_ERR_ARG, "null table array");
+    *tc = cmpc::LinTableConst{td->T, td->mode, t, nu};
     return CMPC_OK;
+}
+
+int cmpc_lin_table_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int nu,
+                             const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const int* nbr,
+                             const double* traj_all, double* A, double* B, double* qlin, double* C, double* h,
+                             void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!td || !tab || !traj_all || !A || !B || !qlin || !C || !h || (d && d->nb > 0 && !nbr))
+        return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::LinConst c;
+    cmpc::LinTableConst tc;
+    int rc = lin_const(ctx, prm, d, &c);
+    if (rc != CMPC_OK) return rc;
+    if ((rc = lin_table_const(ctx, d, nu, td, tab, t, &tc)) != CMPC_OK) return rc;
+    if (d->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    const cmpc::LinTablePtrs p{nbr, tab->A, tab->B, tab->qlin, tab->C, tab->h, traj_all, A, B, qlin, C, h};
+    HIP_TRY(cmpc::lin_table_build_launch(c, tc, p, d->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
+int cmpc_lin_table_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                             const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const double* traj_all,
+                             const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                             const cmpc_mpc_out* out, const cmpc_opts* opts, double* traj_local, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!td || !tab || !traj_all || !traj_local || !dims || !in || !out || !out->z || !in->A || !in->B || !in->x0 ||
+        !in->u_prev || !in->qlin || !in->C || !in->h || (d && d->nb > 0 && !nbr))
+        return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::LinConst c;
+    cmpc::LinTableConst tc;
+    int rc = lin_const(ctx, prm, d, &c);
+    if (rc != CMPC_OK) return rc;
+    if ((rc = lin_table_const(ctx, d, dims->nu, td, tab, t, &tc)) != CMPC_OK) return rc;
+    if ((rc = lin_round_check(ctx, d, dims, w, opts)) != CMPC_OK) return rc;
+    if (d->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const cmpc::LinTablePtrs p{nbr, tab->A, tab->B, tab->qlin, tab->C, tab->h, traj_all, const_cast<double*>(in->A),
+                               const_cast<double*>(in->B), const_cast<double*>(in->qlin), const_cast<double*>(in->C),
+                               const_cast<double*>(in->h)};
+    HIP_TRY(cmpc::lin_table_build_launch(c, tc, p, d->batch, s));
+    return lin_solve_advance(ctx, c, dims, w, in, out, opts, traj_local, stream);
 }
 
 int cmpc_solve_qp_batch(cmpc_ctx* ctx, const cmpc_qp_dims* d, const cmpc_qp_data* in, const cmpc_qp_out* out,

@@ -369,7 +369,24 @@ struct LinPtrs {
     double* h;
 };
 
+// The stage table of a time-varying agent (cmpc_lin_table_build_dev): T rows per agent, read at row(t + k)
+struct LinTableConst {
+    int T, mode, t, nu;
+};
+
+struct LinTablePtrs {
+    const int* nbr;
+    const double *A_tab, *B_tab, *qlin_tab, *C_tab, *h_tab;
+    const double* traj_all;
+    double *A, *B;
+    double* qlin;
+    double* C;
+    double* h;
+};
+
 hipError_t lin_build_launch(const LinConst& c, const LinPtrs& p, int batch, hipStream_t s);
+hipError_t lin_table_build_launch(const LinConst& c, const LinTableConst& tc, const LinTablePtrs& p, int batch,
+                                  hipStream_t s);
 hipError_t lin_advance_launch(const LinConst& c, int ns, int nu, const double* z, double* x0, double* up,
                               double* traj, int batch, hipStream_t s);
 

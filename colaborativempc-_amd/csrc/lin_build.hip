@@ -9,6 +9,8 @@
 //   p_k = qlin_own_k + wq sum_i w_i a_i on (ix, iy)
 // One workgroup (one wavefront) per agent, no LDS, no scratch: the copies go lane by lane over consecutive
 // addresses, the planes one lane per stage with the neighbours in order.
+// lin_table_build_kernel (cmpc_lin_table_build_dev) is the same build for an agent whose future is a stage table:
+// the own data of window stage k come from table row row(t + k), and the A / B windows go out in the same launch.
 #include <cmath>
 
 #include "internal.h"
@@ -16,6 +18,37 @@
 namespace cmpc {
 
 namespace {
+
+// Stage k = 1..N of one agent: the nb planes (row k-1 of the trajectories) into rows mo.. of C / h at row index
+// k-1, and the coverage term (row k) added to the own cost row `qk` of that stage.  The one statement of the
+// family's arithmetic: lin_build_kernel and lin_table_build_kernel differ only in where `qk` comes from.
+__device__ __forceinline__ void lin_stage(const LinConst& c, const double* traj_all, const double* own, const int* nbr,
+                                          int k, const double* qk, double* qlin, double* C, double* h) {
+#pragma clang fp contract(off)
+    const int N = c.N, nx = c.nx, mo = c.mo, nb = c.nb, mc = mo + nb, ix = c.ix, iy = c.iy;
+    const int h1 = k - 1;
+    double* Ck = C + ((size_t)h1 * mc + mo) * nx;
+    double* hk = h + (size_t)h1 * mc + mo;
+    double px = 0.0, py = 0.0;
+    for (int i = 0; i < nb; ++i) {
+        const double* nt = traj_all + (size_t)nbr[i] * (N + 1) * 2;
+        const double ex = own[h1 * 2], ey = own[h1 * 2 + 1];
+        const double nx_ = nt[h1 * 2], ny_ = nt[h1 * 2 + 1];
+        const double dx = nx_ - ex, dy = ny_ - ey;
+        const double nrm = sqrt(dx * dx + dy * dy);
+        const double ax = dx / nrm, ay = dy / nrm;
+        const double bb = -0.5 * (ax * (ex + nx_) + ay * (ey + ny_));
+        const double qx = own[k * 2] - nt[k * 2], qy = own[k * 2 + 1] - nt[k * 2 + 1];
+        const double wgt = (2.0 * c.min_dist - sqrt(qx * qx + qy * qy)) / nb;
+        Ck[(size_t)i * nx + ix] = ax;
+        Ck[(size_t)i * nx + iy] = ay;
+        hk[i] = -c.min_dist / 2 - bb;
+        px = px + c.wq * wgt * ax;
+        py = py + c.wq * wgt * ay;
+    }
+    qlin[(size_t)k * nx + ix] = qk[ix] + px;
+    qlin[(size_t)k * nx + iy] = qk[iy] + py;
+}
 
 __global__ __launch_bounds__(kWave) void lin_build_kernel(const LinConst c, const LinPtrs P) {
 #pragma clang fp contract(off)
@@ -48,30 +81,60 @@ __global__ __launch_bounds__(kWave) void lin_build_kernel(const LinConst c, cons
         if (r < mo) h[i] = ho[(size_t)k1 * mo + r];
     }
     // stage k = 1..N: the nb planes (row k-1 of the trajectories) and the coverage term (row k)
-    for (int k = threadIdx.x + 1; k <= N; k += kWave) {
-        const int h1 = k - 1;
-        double* Ck = C + ((size_t)h1 * mc + mo) * nx;
-        double* hk = h + (size_t)h1 * mc + mo;
-        double px = 0.0, py = 0.0;
-        for (int i = 0; i < nb; ++i) {
-            const double* nt = P.traj_all + (size_t)nbr[i] * (N + 1) * 2;
-            const double ex = own[h1 * 2], ey = own[h1 * 2 + 1];
-            const double nx_ = nt[h1 * 2], ny_ = nt[h1 * 2 + 1];
-            const double dx = nx_ - ex, dy = ny_ - ey;
-            const double nrm = sqrt(dx * dx + dy * dy);
-            const double ax = dx / nrm, ay = dy / nrm;
-            const double bb = -0.5 * (ax * (ex + nx_) + ay * (ey + ny_));
-            const double qx = own[k * 2] - nt[k * 2], qy = own[k * 2 + 1] - nt[k * 2 + 1];
-            const double wgt = (2.0 * c.min_dist - sqrt(qx * qx + qy * qy)) / nb;
-            Ck[(size_t)i * nx + ix] = ax;
-            Ck[(size_t)i * nx + iy] = ay;
-            hk[i] = -c.min_dist / 2 - bb;
-            px = px + c.wq * wgt * ax;
-            py = py + c.wq * wgt * ay;
-        }
-        qlin[(size_t)k * nx + ix] = qo[(size_t)k * nx + ix] + px;
-        qlin[(size_t)k * nx + iy] = qo[(size_t)k * nx + iy] + py;
+    for (int k = threadIdx.x + 1; k <= N; k += kWave)
+        lin_stage(c, P.traj_all, own, nbr, k, qo + (size_t)k * nx, qlin, C, h);
+}
+
+// The stage table's row of window stage k at time t (include/cmpc.h, "stage table"): tau = t + k fits an int
+// (the entry point checks t <= INT_MAX - N)
+__device__ __forceinline__ size_t table_row(const LinTableConst& tc, int k) {
+    const int tau = tc.t + k;
+    return tc.mode == CMPC_TABLE_PERIODIC ? (size_t)(tau % tc.T) : (size_t)(tau < tc.T ? tau : tc.T - 1);
+}
+
+// lin_build_kernel with the own data read through table_row straight from the stage table, and the A / B
+// windows of the round copied into the solver's arrays by the same launch
+__global__ __launch_bounds__(kWave) void lin_table_build_kernel(const LinConst c, const LinTableConst tc,
+                                                                const LinTablePtrs P) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x;
+    const int N = c.N, nx = c.nx, mo = c.mo, nb = c.nb, mc = mo + nb, ix = c.ix, iy = c.iy;
+    const size_t T = (size_t)tc.T, nA = (size_t)nx * nx, nB = (size_t)nx * tc.nu;
+    const double* own = P.traj_all + (size_t)(c.self_offset + b) * (N + 1) * 2;
+    const int* nbr = P.nbr + (size_t)b * nb;
+    const double* At = P.A_tab + (size_t)b * T * nA;
+    const double* Bt = P.B_tab + (size_t)b * T * nB;
+    const double* qt = P.qlin_tab + (size_t)b * T * nx;
+    const double* Ct = P.C_tab + (size_t)b * T * mo * nx;  // (not dereferenced when mo == 0)
+    const double* ht = P.h_tab + (size_t)b * T * mo;
+    double* A = P.A + (size_t)b * N * nA;
+    double* B = P.B + (size_t)b * N * nB;
+    double* qlin = P.qlin + (size_t)b * (N + 1) * nx;
+    double* C = P.C + (size_t)b * N * mc * nx;
+    double* h = P.h + (size_t)b * N * mc;
+
+    // the model's window: stages t .. t+N-1
+    for (size_t i = threadIdx.x; i < (size_t)N * nA; i += kWave) A[i] = At[table_row(tc, (int)(i / nA)) * nA + i % nA];
+    for (size_t i = threadIdx.x; i < (size_t)N * nB; i += kWave) B[i] = Bt[table_row(tc, (int)(i / nB)) * nB + i % nB];
+    // the own cost of stages t .. t+N, except the two position entries of window stages 1..N (the stage lanes)
+    for (size_t i = threadIdx.x; i < (size_t)(N + 1) * nx; i += kWave) {
+        const int s = (int)(i % nx), k = (int)(i / nx);
+        if (k == 0 || (s != ix && s != iy)) qlin[i] = qt[table_row(tc, k) * nx + s];
     }
+    // the own rows of stages t+1 .. t+N, and the zeros of the plane rows
+    for (size_t i = threadIdx.x; i < (size_t)N * mc * nx; i += kWave) {
+        const int s = (int)(i % nx), r = (int)(i / nx % mc), k1 = (int)(i / nx / mc);
+        if (r < mo)
+            C[i] = Ct[(table_row(tc, k1 + 1) * mo + r) * nx + s];
+        else if (s != ix && s != iy)
+            C[i] = 0.0;
+    }
+    for (size_t i = threadIdx.x; i < (size_t)N * mc; i += kWave) {
+        const int r = (int)(i % mc), k1 = (int)(i / mc);
+        if (r < mo) h[i] = ht[table_row(tc, k1 + 1) * mo + r];
+    }
+    for (int k = threadIdx.x + 1; k <= N; k += kWave)
+        lin_stage(c, P.traj_all, own, nbr, k, qt + table_row(tc, k) * nx, qlin, C, h);
 }
 
 // x0 <- x_1, u_prev <- u_0, traj <- predicted (z[ix], z[iy]) for k = 0..N  (z in reference layout); an agent
@@ -99,6 +162,13 @@ __global__ __launch_bounds__(kWave) void lin_advance_kernel(const LinConst c, in
 hipError_t lin_build_launch(const LinConst& c, const LinPtrs& p, int batch, hipStream_t s) {
     if (batch == 0) return hipSuccess;
     hipLaunchKernelGGL(lin_build_kernel, dim3(batch), dim3(kWave), 0, s, c, p);
+    return hipGetLastError();
+}
+
+hipError_t lin_table_build_launch(const LinConst& c, const LinTableConst& tc, const LinTablePtrs& p, int batch,
+                                  hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(lin_table_build_kernel, dim3(batch), dim3(kWave), 0, s, c, tc, p);
     return hipGetLastError();
 }
 

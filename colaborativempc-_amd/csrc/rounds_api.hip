@@ -5,6 +5,7 @@
 //   LPV: [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
 //   DI:  [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 //   LIN: [cmpc_nbr_select_dev ->] cmpc_lin_round_dev -> [cmpc_order_by_iters_dev ->] exchange
+//        (over a stage table: cmpc_lin_table_round_dev at the handle's time, which then moves on one stage)
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's communicator
 // (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).  With the log on
 // (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1] into the
@@ -119,7 +120,12 @@ struct cmpc_di_rounds : SolverRounds {
 struct cmpc_lin_rounds : SolverRounds {
     cmpc_lin_params prm{};
     int mo = 0;
-    double *qlin_own = nullptr, *C_own = nullptr, *h_own = nullptr;  // uploaded once, only read
+    // the own data, only read by the rounds: the fixed window (N + 1 / N / N stages, uploaded once), or the qlin /
+    // C / h rows of a stage table (T stages each)
+    double *qlin_own = nullptr, *C_own = nullptr, *h_own = nullptr;
+    // the stage table of cmpc_lin_rounds_create_table (T == 0: a fixed-window handle) and the next round's time
+    int T = 0, mode = CMPC_TABLE_HOLD, t = 0;
+    double *A_tab = nullptr, *B_tab = nullptr;  // T stages; the round gathers their window into A, B
 };
 
 namespace {
@@ -482,6 +488,92 @@ int history_rounds(SolverRounds* h, int first_round, int count, double* kkt, int
     return CMPC_OK;
 }
 
+// ---- the linear-model handle's two creates ----
+
+// What cmpc_lin_rounds_create and cmpc_lin_rounds_create_table hand lin_create: HOST pointers.  T == 0: A, B,
+// qlin, C, h are the fixed window (N, N, N + 1, N, N stages); T >= 1: the stage table (T stages each).
+struct LinInit {
+    int T, mode, t0;
+    const double *A, *B, *qlin, *C, *h, *x0, *u_prev;
+    const int* nbr;
+    const double* traj;
+};
+
+int lin_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights* w, const cmpc_lin_rounds_dims* dims,
+               const LinInit& in, bool table, const cmpc_opts* opts, cmpc_lin_rounds** out) {
+    const cmpc_lpv_rounds_dims d{dims->n_total, dims->batch, dims->self_offset, dims->N, dims->nb, dims->flags};
+    const cmpc_lin_dims ld{d.batch, d.N, d.nb, d.self_offset, dims->nx, dims->mo};
+    cmpc::LinConst lc;
+    int rc = lin_const(ctx, prm, &ld, &lc);  // the family's own dimension rules first: mo is checked before it is used
+    if (rc != CMPC_OK) return rc;
+    if (dims->nu < 1 || dims->nu > CMPC_MAX_NU || dims->ns < 0 || dims->ns > CMPC_MAX_NS)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (0 <= ns <= 4, 1 <= nu <= 4)");
+    if (table && (in.T < 1 || (in.mode != CMPC_TABLE_HOLD && in.mode != CMPC_TABLE_PERIODIC) || in.t0 < 0 || in.t0 >= in.T))
+        return fail(ctx, CMPC_ERR_ARG, "bad stage table (T >= 1, mode CMPC_TABLE_HOLD or CMPC_TABLE_PERIODIC, 0 <= t0 < T)");
+    rc = check_create(ctx, d, CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT,
+                      in.nbr, opts, dims->mo);
+    if (rc != CMPC_OK) return rc;
+    if (dims->history < 0) return fail(ctx, CMPC_ERR_ARG, "negative history");
+    if (!w->Q || !w->R || !w->dR || (dims->ns && !w->Qs) || !w->u_ub || !w->u_lb ||
+        (dims->mo + d.nb && (!w->row_slack || !w->row_sign)))
+        return fail(ctx, CMPC_ERR_ARG, "null weights");
+    if (!in.A || !in.B || !in.x0 || !in.u_prev || !in.qlin || !in.traj || (dims->mo && (!in.C || !in.h)))
+        return fail(ctx, CMPC_ERR_ARG, "null initial state");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    auto* h = new cmpc_lin_rounds();
+    core_init(h, ctx, d, opts);
+    h->prm = *prm;
+    h->mo = dims->mo;
+    h->history = std::max(dims->history, 1);
+    if (table) {
+        h->T = in.T;
+        h->mode = in.mode;
+        h->t = in.t0;
+    }
+    const int nx = dims->nx, nu = dims->nu, mo = dims->mo, mc = mo + d.nb;
+    h->md = cmpc_mpc_dims{nx, nu, d.N, dims->ns, mc, d.batch};
+    // the stages of the caller's model, cost and row arrays
+    const size_t B = d.batch, N = d.N, SA = table ? in.T : N, Sq = table ? in.T : N + 1, SC = table ? in.T : N;
+    // time-invariant agents: the promise the solver may use.  The fixed window never changes after this; of a
+    // table every row has to agree, since any of them may enter a window (cmpc_lin_rounds_table_write withdraws it)
+    if (stages_lti(in.A, B, SA, (size_t)nx * nx) && stages_lti(in.B, B, SA, (size_t)nx * nu))
+        h->opts.flags |= CMPC_FLAG_LTI;
+    copy_weights(h, w);
+
+    const size_t nb1 = d.nb ? d.nb : 1, T = d.n_total, row = h->traj_row(), H = h->history;
+    const size_t nA = B * N * nx * nx, nB = B * N * nx * nu, nq = B * (N + 1) * nx;
+    const size_t uA = B * SA * nx * nx, uB = B * SA * nx * nu, uq = B * Sq * nx, uC = B * SC * mo * nx, uh = B * SC * mo;
+    const size_t bytes = device_block(
+        &h->mem, {{h->A, nA}, {h->B, nB}, {h->x0, B * nx}, {h->u_prev, B * nu}, {h->qlin_own, uq}, {h->C_own, uC},
+                  {h->h_own, uh}, {h->traj_all, T * row}, {h->traj_local, B * row}, {h->qlin, nq},
+                  {h->C, B * N * mc * nx}, {h->h, B * N * mc}, {h->z, B * nz_mpc(h->md)}, {h->kkt, H * B},
+                  {h->nbr, B * nb1}, {h->iters, H * B}, {h->status, H * B}, {h->order, B},
+                  {h->A_tab, table ? uA : 0}, {h->B_tab, table ? uB : 0}});
+    if (!bytes) {
+        delete h;
+        return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
+    }
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemsetAsync(h->mem, 0, bytes, s);  // a read before the first round returns zeros
+    if (e == hipSuccess) e = upload(table ? h->A_tab : h->A, in.A, 8 * uA, s);
+    if (e == hipSuccess) e = upload(table ? h->B_tab : h->B, in.B, 8 * uB, s);
+    if (e == hipSuccess) e = upload(h->x0, in.x0, 8 * B * nx, s);
+    if (e == hipSuccess) e = upload(h->u_prev, in.u_prev, 8 * B * nu, s);
+    if (e == hipSuccess) e = upload(h->qlin_own, in.qlin, 8 * uq, s);
+    if (e == hipSuccess && mo) e = upload(h->C_own, in.C, 8 * uC, s);
+    if (e == hipSuccess && mo) e = upload(h->h_own, in.h, 8 * uh, s);
+    if (e == hipSuccess) e = upload(h->traj_all, in.traj, 8 * T * row, s);
+    if (e == hipSuccess && d.nb) e = upload(h->nbr, in.nbr, 4 * B * d.nb, s);
+    if ((e = finish_uploads(h, e)) != hipSuccess) {
+        (void)hipFree(h->mem);
+        delete h;
+        return hip_fail(ctx, e, "cmpc_lin_rounds_create: upload");
+    }
+    *out = h;
+    return CMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -729,76 +821,85 @@ int cmpc_lin_rounds_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc
     if (!ctx) return CMPC_ERR_ARG;
     if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
     *out = nullptr;
-    const cmpc_lpv_rounds_dims d{dims->n_total, dims->batch, dims->self_offset, dims->N, dims->nb, dims->flags};
-    const cmpc_lin_dims ld{d.batch, d.N, d.nb, d.self_offset, dims->nx, dims->mo};
-    cmpc::LinConst lc;
-    int rc = lin_const(ctx, prm, &ld, &lc);  // the family's own dimension rules first: mo is checked before it is used
-    if (rc != CMPC_OK) return rc;
-    if (dims->nu < 1 || dims->nu > CMPC_MAX_NU || dims->ns < 0 || dims->ns > CMPC_MAX_NS)
-        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (0 <= ns <= 4, 1 <= nu <= 4)");
-    rc = check_create(ctx, d, CMPC_ROUNDS_HOST_EXCHANGE | CMPC_ROUNDS_NO_HALT | CMPC_ROUNDS_RESELECT | CMPC_ROUNDS_LPT,
-                      in->nbr, opts, dims->mo);
-    if (rc != CMPC_OK) return rc;
-    if (dims->history < 0) return fail(ctx, CMPC_ERR_ARG, "negative history");
-    if (!w->Q || !w->R || !w->dR || (dims->ns && !w->Qs) || !w->u_ub || !w->u_lb ||
-        (dims->mo + d.nb && (!w->row_slack || !w->row_sign)))
-        return fail(ctx, CMPC_ERR_ARG, "null weights");
-    if (!in->A || !in->B || !in->x0 || !in->u_prev || !in->qlin_own || !in->traj || (dims->mo && (!in->C_own || !in->h_own)))
-        return fail(ctx, CMPC_ERR_ARG, "null initial state");
-    HIP_TRY(hipSetDevice(ctx->device));
+    const LinInit li{0, 0, 0, in->A, in->B, in->qlin_own, in->C_own, in->h_own, in->x0, in->u_prev, in->nbr, in->traj};
+    return lin_create(ctx, prm, w, dims, li, false, opts, out);
+}
 
-    auto* h = new cmpc_lin_rounds();
-    core_init(h, ctx, d, opts);
-    h->prm = *prm;
-    h->mo = dims->mo;
-    h->history = std::max(dims->history, 1);
-    const int nx = dims->nx, nu = dims->nu, mo = dims->mo, mc = mo + d.nb;
-    h->md = cmpc_mpc_dims{nx, nu, d.N, dims->ns, mc, d.batch};
-    // time-invariant agents (the handle never changes A or B after this): the promise the solver may use
-    if (stages_lti(in->A, d.batch, d.N, (size_t)nx * nx) && stages_lti(in->B, d.batch, d.N, (size_t)nx * nu))
-        h->opts.flags |= CMPC_FLAG_LTI;
-    copy_weights(h, w);
-
-    const size_t B = d.batch, N = d.N, nb1 = d.nb ? d.nb : 1, T = d.n_total, row = h->traj_row(), H = h->history;
-    const size_t nA = B * N * nx * nx, nB = B * N * nx * nu, nq = B * (N + 1) * nx, nC = B * N * mo * nx, nh = B * N * mo;
-    const size_t bytes = device_block(
-        &h->mem, {{h->A, nA}, {h->B, nB}, {h->x0, B * nx}, {h->u_prev, B * nu}, {h->qlin_own, nq}, {h->C_own, nC},
-                  {h->h_own, nh}, {h->traj_all, T * row}, {h->traj_local, B * row}, {h->qlin, nq},
-                  {h->C, B * N * mc * nx}, {h->h, B * N * mc}, {h->z, B * nz_mpc(h->md)}, {h->kkt, H * B},
-                  {h->nbr, B * nb1}, {h->iters, H * B}, {h->status, H * B}, {h->order, B}});
-    if (!bytes) {
-        delete h;
-        return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
-    }
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemsetAsync(h->mem, 0, bytes, s);  // a read before the first round returns zeros
-    if (e == hipSuccess) e = upload(h->A, in->A, 8 * nA, s);
-    if (e == hipSuccess) e = upload(h->B, in->B, 8 * nB, s);
-    if (e == hipSuccess) e = upload(h->x0, in->x0, 8 * B * nx, s);
-    if (e == hipSuccess) e = upload(h->u_prev, in->u_prev, 8 * B * nu, s);
-    if (e == hipSuccess) e = upload(h->qlin_own, in->qlin_own, 8 * nq, s);
-    if (e == hipSuccess && mo) e = upload(h->C_own, in->C_own, 8 * nC, s);
-    if (e == hipSuccess && mo) e = upload(h->h_own, in->h_own, 8 * nh, s);
-    if (e == hipSuccess) e = upload(h->traj_all, in->traj, 8 * T * row, s);
-    if (e == hipSuccess && d.nb) e = upload(h->nbr, in->nbr, 4 * B * d.nb, s);
-    if ((e = finish_uploads(h, e)) != hipSuccess) {
-        (void)hipFree(h->mem);
-        delete h;
-        return hip_fail(ctx, e, "cmpc_lin_rounds_create: upload");
-    }
-    *out = h;
-    return CMPC_OK;
+// the same handle over a stage table: the round's window slides one stage per round
+int cmpc_lin_rounds_create_table(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights* w,
+                                 const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_table_init* in,
+                                 const cmpc_opts* opts, cmpc_lin_rounds** out) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    *out = nullptr;
+    const LinInit li{in->T, in->mode, in->t0, in->A, in->B, in->qlin, in->C, in->h, in->x0, in->u_prev, in->nbr, in->traj};
+    return lin_create(ctx, prm, w, dims, li, true, opts, out);
 }
 
 int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
     if (!h) return CMPC_ERR_ARG;
     const cmpc_lin_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->md.nx, h->mo};
+    if (h->T) {  // a stage table: the window at the handle's time, which a round that ran moves on
+        const cmpc_lin_table_dims td{h->T, h->mode};
+        const cmpc_lin_table tab{h->A_tab, h->B_tab, h->qlin_own, h->C_own, h->h_own};
+        return step_rounds(h, rounds, rounds_done, "cmpc_lin_rounds_step: log event",
+                           [&](const cmpc_mpc_data* din, const cmpc_mpc_out* dout, hipStream_t s) {
+                               const int rc = cmpc_lin_table_round_dev(h->ctx, &h->prm, &rd, h->nbr, &td, &tab, h->t,
+                                                                       h->traj_all, &h->md, &h->w, din, dout, &h->opts,
+                                                                       h->traj_local, s);
+                               if (rc == CMPC_OK)
+                                   h->t = h->mode == CMPC_TABLE_PERIODIC ? (h->t + 1) % h->T : std::min(h->t + 1, h->T - 1);
+                               return rc;
+                           });
+    }
     const cmpc_lin_own own{h->qlin_own, h->C_own, h->h_own};
     return step_rounds(h, rounds, rounds_done, "cmpc_lin_rounds_step: log event",
                        [&](const cmpc_mpc_data* din, const cmpc_mpc_out* dout, hipStream_t s) {
                            return cmpc_lin_round_dev(h->ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, &h->md, &h->w,
                                                      din, dout, &h->opts, h->traj_local, s);
                        });
+}
+
+int cmpc_lin_rounds_get_time(cmpc_lin_rounds* h, int* t) {
+    if (!h) return CMPC_ERR_ARG;
+    if (!t) return fail(h->ctx, CMPC_ERR_ARG, "null output");
+    *t = h->t;  // (0 on a fixed-window handle)
+    return CMPC_OK;
+}
+
+int cmpc_lin_rounds_set_time(cmpc_lin_rounds* h, int t) {
+    if (!h) return CMPC_ERR_ARG;
+    if (!h->T) return fail(h->ctx, CMPC_ERR_ARG, "a fixed-window handle has no time (cmpc_lin_rounds_create_table)");
+    if (t < 0 || t >= h->T) return fail(h->ctx, CMPC_ERR_ARG, "bad table time (0 <= t < T)");
+    h->t = t;
+    return CMPC_OK;
+}
+
+// HOST rows batch x count x ... -> rows [first_row, first_row + count) of every agent's table
+int cmpc_lin_rounds_table_write(cmpc_lin_rounds* h, int first_row, int count, const cmpc_lin_table* rows) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!h->T) return fail(ctx, CMPC_ERR_ARG, "a fixed-window handle has no table (cmpc_lin_rounds_create_table)");
+    if (!rows) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    if (first_row < 0 || count < 0 || (long long)first_row + count > h->T)
+        return fail(ctx, CMPC_ERR_ARG, "table rows out of range (no wrap: split a wrapped write)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nx = h->md.nx, nu = h->md.nu, mo = h->mo;
+    // one agent's `count` rows are contiguous on both sides; agents are T rows apart in the table
+    auto put = [&](double* tab, const double* src, size_t per) {
+        if (!src || !per || !count) return hipSuccess;
+        return hipMemcpy2DAsync(tab + (size_t)first_row * per, 8 * per * h->T, src, 8 * per * count, 8 * per * count,
+                                h->d.batch, hipMemcpyHostToDevice, s);
+    };
+    if (count && (rows->A || rows->B)) h->opts.flags &= ~CMPC_FLAG_LTI;  // the rows may differ now
+    HIP_TRY(put(h->A_tab, rows->A, nx * nx));
+    HIP_TRY(put(h->B_tab, rows->B, nx * nu));
+    HIP_TRY(put(h->qlin_own, rows->qlin, nx));
+    HIP_TRY(put(h->C_own, rows->C, mo * nx));
+    HIP_TRY(put(h->h_own, rows->h, mo));
+    HIP_TRY(hipStreamSynchronize(s));
+    return CMPC_OK;
 }
 
 int cmpc_lin_rounds_read(cmpc_lin_rounds* h, const cmpc_lin_rounds_out* o) { return read_rounds(h, o); }

@@ -54,7 +54,10 @@ extern "C" {
                                 CMPC_FLAG_CERTIFY_ROWS, cmpc_mpc_cert_rows, cmpc_mpc_certify_rows[_dev];
                                 CMPC_FLAG_LPV, CMPC_FLAG_LPV_AUTO, cmpc_mpc_lpv_level[_dev];
                                 CMPC_FLAG_LPV_SPLIT, cmpc_mpc_lpv_split_dev;
-                                cmpc_lin_build_dev, cmpc_lin_advance_dev, cmpc_lin_round_dev, cmpc_lin_rounds_* */
+                                cmpc_lin_build_dev, cmpc_lin_advance_dev, cmpc_lin_round_dev, cmpc_lin_rounds_*;
+                                CMPC_TABLE_HOLD / _PERIODIC, cmpc_lin_table_dims, cmpc_lin_table,
+                                cmpc_lin_table_build_dev, cmpc_lin_table_round_dev, cmpc_lin_rounds_table_init,
+                                cmpc_lin_rounds_create_table, cmpc_lin_rounds_get_time / _set_time / _table_write */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -1016,6 +1019,86 @@ int cmpc_lin_rounds_destroy(cmpc_lin_rounds* h);
 int cmpc_lin_rounds_log_enable(cmpc_lin_rounds* h, int capacity, int flags);
 int cmpc_lin_rounds_log_range(cmpc_lin_rounds* h, int* first_round, int* count);
 int cmpc_lin_rounds_log_read(cmpc_lin_rounds* h, int first_round, int count, const cmpc_rounds_log* host_out);
+
+/* ------------------------------------------------------------------------
+ * Time-varying agents of the family: a stage table that slides one stage per round.  A round is a control step,
+ * so round r of an agent whose model, reference or bounds change along its future plans with A_r .. A_{r+N-1} and
+ * the own data of stages r .. r+N.  The future is given as a table of stages (a successive-linearisation table, a
+ * periodic model, a reference-speed profile, a bound that tightens along a road).
+ *
+ * A STAGE TABLE holds, per agent, T >= 1 rows indexed by absolute stage tau:
+ *   A    batch x T x nx x nx     x_{tau+1} = A_tau x_tau + B_tau u_tau
+ *   B    batch x T x nx x nu
+ *   qlin batch x T x nx          own linear cost on x_tau
+ *   C    batch x T x mo x nx     own rows on x_tau      (NULL when mo == 0)
+ *   h    batch x T x mo
+ * row(tau) = tau mod T with CMPC_TABLE_PERIODIC, min(tau, T-1) with CMPC_TABLE_HOLD (past its end the table holds
+ * its last stage).  The window at time t >= 0 is
+ *   A_win[b,k]    = A[b,row(t+k)]                      k = 0..N-1   (B likewise)
+ *   qlin_own[b,k] = qlin[b,row(t+k)]                   k = 0..N
+ *   C_own[b,k-1]  = C[b,row(t+k)],  h_own likewise     k = 1..N
+ * every value copied bit for bit (-0.0 stays -0.0, a NaN stays a NaN); N + 1 > T is allowed (HOLD repeats the last
+ * row, PERIODIC wraps as often as needed).  cmpc.scenarios.lin_table_rows / lin_window are the numpy statement.
+ *
+ * cmpc_lin_table_build_dev: a round's whole build in one launch.  A_win, B_win are written into A (batch x N x nx
+ * x nx) and B (batch x N x nx x nu), and qlin, C, h are exactly cmpc_lin_build_dev's rule applied to that window,
+ * the own data read through row() straight from the table (no intermediate window, no second launch).  One
+ * workgroup per agent, no LDS, no scratch, stream-ordered, graph-capturable; t is a launch argument.
+ *
+ * cmpc_lin_table_round_dev: cmpc_lin_round_dev with that build: cmpc_lin_table_build_dev into data->A / B / qlin /
+ * C / h (written despite the const), cmpc_solve_mpc_batch_dev, cmpc_lin_advance_dev into data->x0 / u_prev and
+ * traj_local.  Every argument rule, the solver's included, is checked before the first launch; solver flags
+ * mean what they mean on cmpc_solve_mpc_batch_dev (CMPC_FLAG_LTI is the caller's promise about the WINDOW).
+ *
+ * CMPC_ERR_ARG: what cmpc_lin_build_dev / cmpc_lin_round_dev list; T < 1; a mode other than 0 or 1; t < 0 or
+ * t > INT_MAX - N; nu outside 1..CMPC_MAX_NU (the round: mpc_dims->nu is the table's); a NULL table array (C / h
+ * may be NULL when mo == 0); a NULL output.  batch == 0: CMPC_OK without a launch.
+ * ---------------------------------------------------------------------- */
+#define CMPC_TABLE_HOLD 0
+#define CMPC_TABLE_PERIODIC 1
+typedef struct { int T, mode; } cmpc_lin_table_dims;
+typedef struct { const double *A, *B, *qlin, *C, *h; } cmpc_lin_table;   /* DEVICE pointers, only read */
+
+int cmpc_lin_table_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* dims, int nu,
+                             const cmpc_lin_table_dims* tdims, const cmpc_lin_table* table, int t, const int* nbr,
+                             const double* traj_all, double* A, double* B, double* qlin, double* C, double* h,
+                             void* hip_stream);
+int cmpc_lin_table_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* ldims, const int* nbr,
+                             const cmpc_lin_table_dims* tdims, const cmpc_lin_table* table, int t,
+                             const double* traj_all, const cmpc_mpc_dims* mpc_dims, const cmpc_mpc_weights* w,
+                             const cmpc_mpc_data* data, const cmpc_mpc_out* out, const cmpc_opts* opts,
+                             double* traj_local /* batch x (N+1) x 2 */, void* hip_stream);
+
+/* The round handle over a stage table: cmpc_lin_rounds_create_table returns the handle type of
+ * cmpc_lin_rounds_create, so _step, _read, _history, _get_traj / _set_traj, _set_state, _destroy and the log
+ * functions work on it unchanged.  The handle keeps the table on the device and a time t (t0 at create); step 2 of
+ * a round is cmpc_lin_table_round_dev at t.  After a round that ran, t <- (t + 1) mod T (PERIODIC) or
+ * min(t + 1, T - 1) (HOLD: from there every window row already reads the last stage); a round whose solver call
+ * returns an API error does not advance t.  CMPC_FLAG_LTI is set only when every row of the whole A and B tables
+ * is bit-equal to row 0 (and finite); a _table_write that carries A or B clears it.
+ *   _get_time / _set_time: the time of the next round; _set_time takes 0 <= t < T.
+ *   _table_write: HOST arrays batch x count x ... (the table's shapes with count for T) into rows [first_row,
+ *     first_row + count) of every agent; no wrap (the caller splits a wrapped write); any array may be NULL: that
+ *     part stays as it was.  Synchronises.  A PERIODIC table whose consumed rows the host overwrites is a ring
+ *     for online re-linearisation.
+ * On a handle of cmpc_lin_rounds_create _get_time gives 0; _set_time and _table_write return CMPC_ERR_ARG.
+ * CMPC_ERR_ARG at create: what cmpc_lin_rounds_create lists (the table arrays for its A, B, qlin_own, C_own,
+ * h_own); T < 1; a mode other than 0 or 1; t0 < 0 or t0 >= T.  _table_write: first_row < 0, count < 0,
+ * first_row + count > T, a NULL struct. */
+typedef struct {    /* HOST pointers, this rank's agents, copied at create */
+    int T, mode, t0;
+    const double *A, *B, *qlin, *C, *h;   /* the table, shapes as above (C / h may be NULL when mo == 0) */
+    const double *x0, *u_prev;            /* as cmpc_lin_rounds_init */
+    const int* nbr;
+    const double* traj;
+} cmpc_lin_rounds_table_init;
+
+int cmpc_lin_rounds_create_table(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights* w,
+                                 const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_table_init* init,
+                                 const cmpc_opts* opts, cmpc_lin_rounds** out);
+int cmpc_lin_rounds_get_time(cmpc_lin_rounds* h, int* t);
+int cmpc_lin_rounds_set_time(cmpc_lin_rounds* h, int t);
+int cmpc_lin_rounds_table_write(cmpc_lin_rounds* h, int first_row, int count, const cmpc_lin_table* host_rows);
 
 
 /* ------------------------------------------------------------------------
