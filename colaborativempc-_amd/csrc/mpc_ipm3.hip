@@ -198,6 +198,29 @@ constexpr bool kDiagAddr = true;
 #endif
 template <int T, int NX, int NU>
 __host__ __device__ constexpr bool dg_addr_on() { return kDiagAddr && dg_on<T>() && T != 2; }
+//  tr_on       the time-invariant instantiations hold A (and, in the forward recursions, B) in registers through a
+//              stage recursion: the lane reads its row or column of stage 0 once per call, and a stage fetches
+//              only its y_k or u_k ahead.  Every stage of the image holds the same doubles, so each fma has the
+//              operands, the order and the even/odd partial sums it had.  Read at the start of each call, not
+//              held across the iteration loop (the register file has no room for six more doubles there).
+// -DCMPC_NO_TI_REGS restores the per-stage fetches (A/B builds).
+#ifdef CMPC_NO_TI_REGS
+constexpr bool kTiRegs = false;
+#else
+constexpr bool kTiRegs = true;
+#endif
+template <bool TI, int T>
+__host__ __device__ constexpr bool tr_on() { return TI && kTiRegs; }
+//  trb_on      ... and the once-per-solve builds: phi_build and psi_build read A once, and the table's build
+//              keeps its columns in registers until one store pass after the recursion (below).
+// -DCMPC_NO_TI_REGS_BUILD restores the builds alone.
+#ifdef CMPC_NO_TI_REGS_BUILD
+constexpr bool kTiRegsBuild = false;
+#else
+constexpr bool kTiRegsBuild = true;
+#endif
+template <bool TI, int T>
+__host__ __device__ constexpr bool trb_on() { return tr_on<TI, T>() && kTiRegsBuild; }
 constexpr int kTfW = 8;  // doubles per stage of the weights' fragment image
 constexpr int kTfG = 6;  // doubles per column of the table's fragment image
 template <int NU>
@@ -303,15 +326,24 @@ __host__ __device__ constexpr int ti_b(int k, int r, int j) {
 // row by DPP row_newbcast.  A stage's A row and B u term are fetched two stages ahead into
 // rotating register sets (unrolled by three: no copies, no branches; the fetch index is clamped
 // instead of guarded).  Every lane stores: duplicates write equal values.
-template <int NX, int NU, bool LS = false, bool TI = false>
+// TR (tr_on): A's row s and the lane's row of B are read once; a stage fetches only its B u term.
+template <int NX, int NU, bool LS = false, bool TI = false, bool TR = false>
 __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double* B, const double* x0,
                                      const double* U, double* X) {
     static_assert(NX <= 16, "row broadcast");
     constexpr int NA = LS ? 3 : NX;  // columns of the stage image (LS: D_k, A_k = I + D_k)
+    static_assert(!TR || (TI && !LS && 64 % NX == 0), "TR: a lane's row of B is the same in every pass");
     const int s = (l & 15) < NX ? (l & 15) : 0;
     double xr = x0 ? x0[s] : 0.0;
     X[s] = xr;
     if (N <= 0) return;
+    double ac[NA], bc[NU];
+    if constexpr (TR) {
+#pragma unroll
+        for (int t = 0; t < NA; ++t) ac[t] = A[s * NA + t];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) bc[j] = B[ti_b<NX, NU, true>(0, l % NX, j)];
+    }
     // B_k u_k of every stage first, in parallel (off the chain), into X_{k+1}'s slot; the
     // recursion then adds A_k x_k to it in place (the slot is fetched before it is overwritten)
     for (int i = l; i < N * NX; i += 64) {
@@ -324,14 +356,16 @@ __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double
             v = r < 3 ? v : 0.0;
         } else {
 #pragma unroll
-            for (int j = 0; j < NU; ++j) v = fma(B[ti_b<NX, NU, TI>(k, r, j)], U[k * NU + j], v);
+            for (int j = 0; j < NU; ++j) v = fma(TR ? bc[j] : B[ti_b<NX, NU, TI>(k, r, j)], U[k * NU + j], v);
         }
         X[NX + i] = v;
     }
     wsync();
     auto fetch = [&](int k, double* av, double* bv) __attribute__((always_inline)) {
+        if constexpr (!TR) {
 #pragma unroll
-        for (int t = 0; t < NA; ++t) av[t] = A[(k * NX + s) * NA + t];
+            for (int t = 0; t < NA; ++t) av[t] = A[(k * NX + s) * NA + t];
+        }
         bv[0] = X[(k + 1) * NX + s];
     };
     auto step = [&](int k, const double* av, const double* bv) __attribute__((always_inline)) {
@@ -339,8 +373,8 @@ __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double
         const double xs = dpp_settled(xr);
         static_for<0, NA>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) v1 = fma_bcast16s<tt>(av[tt], xs, v1);
-            else v0 = fma_bcast16s<tt>(av[tt], xs, v0);
+            if constexpr (tt & 1) v1 = fma_bcast16s<tt>(TR ? ac[tt] : av[tt], xs, v1);
+            else v0 = fma_bcast16s<tt>(TR ? ac[tt] : av[tt], xs, v0);
         });
         if constexpr (LS) xr = (v0 + v1) + xr;  // x_{k+1} = x_k + D_k x_k + B_k u_k
         else xr = v0 + v1;
@@ -370,20 +404,27 @@ __device__ __forceinline__ void fwd3(int l, int N, const double* A, const double
 
 // Phi_k for k in (a_1, N] (see seg_a): rows 1..3 build their segment's transitions in parallel, lane
 // s of the row holding row s of Phi (Phi_{a_q} = I, Phi_{k+1} = A_k Phi_k); stored at slot k - a_1 - 1.
-template <int NX>
+// TR (tr_on): A's row s is read once.
+template <int NX, bool TR = false>
 __device__ __forceinline__ void phi_build(int l, int N, const double* A, double* Phi) {
     const int q = l >> 4, s = (l & 15) < NX ? (l & 15) : 0;
     const int a1 = seg_a(1, N), a = seg_a(q, N), e = seg_a(q + 1, N);
-    double ph[NX];
+    double ph[NX], ar[NX];
 #pragma unroll
     for (int t = 0; t < NX; ++t) ph[t] = (s == t) ? 1.0 : 0.0;
+    if constexpr (TR) {
+#pragma unroll
+        for (int t = 0; t < NX; ++t) ar[t] = A[s * NX + t];
+    }
     for (int i = 0; i < a1; ++i) {  // a_1 = the longest segment
         const int k = a + i;
         const bool valid = q >= 1 && k < e;
         const int kc = valid ? k : a1;
-        double ar[NX], nw[NX];
+        double nw[NX];
+        if constexpr (!TR) {
 #pragma unroll
-        for (int t = 0; t < NX; ++t) ar[t] = A[(kc * NX + s) * NX + t];
+            for (int t = 0; t < NX; ++t) ar[t] = A[(kc * NX + s) * NX + t];
+        }
         static_for<0, NX>([&](auto c_c) __attribute__((always_inline)) {
             constexpr int cc = decltype(c_c)::value;
             double v = 0.0;
@@ -412,7 +453,8 @@ __device__ __forceinline__ double phi_apply(const double* phr, const double* xa,
 }
 
 // fwd3 (x_0 = x0 or 0, x_{k+1} = A_k x_k + B_k u_k) by segments (seg_a, phi_build); X, U, A, B as fwd3.
-template <int NX, int NU, bool TI = false>
+// TR (tr_on): A's row s and B's row s are read once; a stage fetches only its u_k.
+template <int NX, int NU, bool TI = false, bool TR = false>
 __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const double* B, const double* x0,
                                         const double* U, double* X, const double* Phi) {
     static_assert(NX <= 16, "row broadcast");
@@ -422,13 +464,23 @@ __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const dou
     // finished row repeats its last stage without changing its state (clamped fetch, select, equal store)
     double xr = (q == 0 && x0) ? x0[s] : 0.0;
     if (q == 0) X[s] = xr;
+    static_assert(!TR || TI, "TR: time-invariant A and B");
+    double abc[NX + NU];
+    if constexpr (TR) {
+#pragma unroll
+        for (int t = 0; t < NX; ++t) abc[t] = A[s * NX + t];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) abc[NX + j] = B[ti_b<NX, NU, true>(0, s, j)];
+    }
     auto fetch = [&](int i, double* av) __attribute__((always_inline)) {
         const int k = a + i < e ? a + i : e - 1;
+        if constexpr (!TR) {
 #pragma unroll
-        for (int t = 0; t < NX; ++t) av[t] = A[(k * NX + s) * NX + t];
+            for (int t = 0; t < NX; ++t) av[t] = A[(k * NX + s) * NX + t];
+        }
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
-            av[NX + j] = B[ti_b<NX, NU, TI>(k, s, j)];
+            if constexpr (!TR) av[NX + j] = B[ti_b<NX, NU, TI>(k, s, j)];
             av[NX + NU + j] = U[k * NU + j];
         }
     };
@@ -436,12 +488,12 @@ __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const dou
         const int k = a + i < e ? a + i : e - 1;
         double v0 = 0.0, v1 = 0.0;
 #pragma unroll
-        for (int j = 0; j < NU; ++j) v0 = fma(av[NX + j], av[NX + NU + j], v0);
+        for (int j = 0; j < NU; ++j) v0 = fma(TR ? abc[NX + j] : av[NX + j], av[NX + NU + j], v0);
         const double xs = dpp_settled(xr);
         static_for<0, NX>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) v1 = fma_bcast16s<tt>(av[tt], xs, v1);
-            else v0 = fma_bcast16s<tt>(av[tt], xs, v0);
+            if constexpr (tt & 1) v1 = fma_bcast16s<tt>(TR ? abc[tt] : av[tt], xs, v1);
+            else v0 = fma_bcast16s<tt>(TR ? abc[tt] : av[tt], xs, v0);
         });
         xr = (a + i < e) ? v0 + v1 : xr;
         X[(k + 1) * NX + s] = xr;
@@ -500,20 +552,27 @@ __device__ __forceinline__ void fwd3seg(int l, int N, const double* A, const dou
 // Psi'_k (transposed) for k in [1, b_3): x_{b_{q+1}} = Psi_k x_k, the transition of stages k ..
 // b_{q+1} - 1 of segment q (seg_b); rows 0..2 build their segment's in parallel from the top
 // (Psi'_k = A_k' Psi'_{k+1}), lane s holding row s; stored at slot k - 1.
-template <int NX>
+// TR (tr_on): A's column s is read once.
+template <int NX, bool TR = false>
 __device__ __forceinline__ void psi_build(int l, int N, const double* A, double* Pst) {
     const int q = l >> 4, s = (l & 15) < NX ? (l & 15) : 0;
     const int b = seg_b(q, N), e = seg_b(q + 1, N), len = seg_b(1, N) - 1;
-    double tr[NX];
+    double tr[NX], at[NX];
 #pragma unroll
     for (int c = 0; c < NX; ++c) tr[c] = (s == c) ? 1.0 : 0.0;
+    if constexpr (TR) {
+#pragma unroll
+        for (int t = 0; t < NX; ++t) at[t] = A[t * NX + s];
+    }
     for (int i = 0; i < len; ++i) {
         const int k = e - 1 - i;
         const bool valid = q <= 2 && k >= b;
         const int kc = valid ? k : 1;
-        double at[NX], nw[NX];
+        double nw[NX];
+        if constexpr (!TR) {
 #pragma unroll
-        for (int t = 0; t < NX; ++t) at[t] = A[(kc * NX + t) * NX + s];
+            for (int t = 0; t < NX; ++t) at[t] = A[(kc * NX + t) * NX + s];
+        }
         static_for<0, NX>([&](auto c_c) __attribute__((always_inline)) {
             constexpr int cc = decltype(c_c)::value;
             double v = 0.0;
@@ -536,16 +595,24 @@ __device__ __forceinline__ void psi_build(int l, int N, const double* A, double*
 // psi3 (psi_N = y_N, psi_k = y_k + A_k' psi_{k+1}, k = N-1 .. 1, over y in place) by segments: each row
 // runs its segment from psi^loc = 0 above it (the top one from psi_N = y_N), a two-step chain carries
 // psi down the segment tops, each row corrects its stages, psi_k = psi^loc_k + Psi'_k psi_{b_{q+1}}.
-template <int NX>
+// TR (tr_on): A's column s is read once; a stage fetches only its y_k.
+template <int NX, bool TR = false>
 __device__ __forceinline__ void psi3seg(int l, int N, const double* A, double* y, const double* Pst) {
     const int q = l >> 4, j = l & 15, s = j < NX ? j : 0;
     const int b = seg_b(q, N), e = seg_b(q + 1, N), len = seg_b(1, N) - 1;
     double pr = 0.0;  // psi^loc_{k+1}: zero above the segment
+    double ac[NX];
+    if constexpr (TR) {
+#pragma unroll
+        for (int t = 0; t < NX; ++t) ac[t] = A[t * NX + s];
+    }
     auto fetch = [&](int i, double* av) __attribute__((always_inline)) {
         const int k = e - 1 - i >= b ? e - 1 - i : b;
-        const int ka = k < N ? k : N - 1;  // psi_N = y_N: A_N does not exist (pr = 0 there)
+        if constexpr (!TR) {
+            const int ka = k < N ? k : N - 1;  // psi_N = y_N: A_N does not exist (pr = 0 there)
 #pragma unroll
-        for (int t = 0; t < NX; ++t) av[t] = A[(ka * NX + t) * NX + s];
+            for (int t = 0; t < NX; ++t) av[t] = A[(ka * NX + t) * NX + s];
+        }
         av[NX] = y[k * NX + s];
     };
     auto step = [&](int i, const double* av) __attribute__((always_inline)) {
@@ -554,8 +621,8 @@ __device__ __forceinline__ void psi3seg(int l, int N, const double* A, double* y
         const double ps = dpp_settled(pr);
         static_for<0, NX>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) p1 = fma_bcast16s<tt>(av[tt], ps, p1);
-            else p0 = fma_bcast16s<tt>(av[tt], ps, p0);
+            if constexpr (tt & 1) p1 = fma_bcast16s<tt>(TR ? ac[tt] : av[tt], ps, p1);
+            else p0 = fma_bcast16s<tt>(TR ? ac[tt] : av[tt], ps, p0);
         });
         pr = (e - 1 - i >= b) ? p0 + p1 : pr;
         y[k * NX + s] = pr;
@@ -614,8 +681,10 @@ __device__ __forceinline__ void psi3seg(int l, int N, const double* A, double* y
 // psi_k overwrites it).  The products o_k = B_k' psi_{k+1} are independent of one another and
 // are formed afterwards by the lanes that own u_k (bpsi3), off the recursion's chain.  The
 // operation order is the fused recursion's (even/odd partial sums), so the bits are unchanged.
-template <int NX, bool LS = false>
+// TR (tr_on): A's column s is read once; a stage fetches only its y_k.
+template <int NX, bool LS = false, bool TR = false>
 __device__ __forceinline__ void psi3(int l, int N, const double* A, double* y0, double* y1) {
+    static_assert(!TR || !LS, "TR: the dense stage image");
     static_assert(NX <= 16, "row broadcast");
     const int h = l >> 5, s = l & 15;
     const int sx = s < NX ? s : 0;
@@ -626,9 +695,16 @@ __device__ __forceinline__ void psi3(int l, int N, const double* A, double* y0, 
     // of D and discard it (branch-free)
     const int sd = sx < 3 ? sx : 0;
     const double dmask = sx < 3 ? 1.0 : 0.0;
-    auto fetch = [&](int k, double* av, double& yv) __attribute__((always_inline)) {
+    double ac[NX];
+    if constexpr (TR) {
 #pragma unroll
-        for (int t = 0; t < NX; ++t) av[t] = LS ? A[(k * NX + t) * 3 + sd] : A[(k * NX + t) * NX + sx];
+        for (int t = 0; t < NX; ++t) ac[t] = A[t * NX + sx];
+    }
+    auto fetch = [&](int k, double* av, double& yv) __attribute__((always_inline)) {
+        if constexpr (!TR) {
+#pragma unroll
+            for (int t = 0; t < NX; ++t) av[t] = LS ? A[(k * NX + t) * 3 + sd] : A[(k * NX + t) * NX + sx];
+        }
         yv = y[k * NX + sx];
     };
     auto step = [&](int k, const double* av, double yk) __attribute__((always_inline)) {
@@ -636,8 +712,8 @@ __device__ __forceinline__ void psi3(int l, int N, const double* A, double* y0, 
         const double ps = dpp_settled(pr);
         static_for<0, NX>([&](auto t) __attribute__((always_inline)) {
             constexpr int tt = decltype(t)::value;
-            if constexpr (tt & 1) p1 = fma_bcast16s<tt>(av[tt], ps, p1);
-            else p0 = fma_bcast16s<tt>(av[tt], ps, p0);
+            if constexpr (tt & 1) p1 = fma_bcast16s<tt>(TR ? ac[tt] : av[tt], ps, p1);
+            else p0 = fma_bcast16s<tt>(TR ? ac[tt] : av[tt], ps, p0);
         });
         if constexpr (LS) pr = fma(dmask, p0 + p1, yk + pr);
         else pr = p0 + p1;
@@ -903,17 +979,24 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
 #define ACT(r) ((actm >> (r)) & 1u)
     if constexpr (TI) {
         // the table: G[d + 1] = A G[d] from G[0] = B by the K build's own chain (v = 0; v = fma(A[s][u], g[u], v)),
-        // once per solve; lane ic < NU carries column ic
-        const int ic = l < NU ? l : 0;
-        double ar[NX * NX], g[NX];
+        // once per solve; lane ic < NU carries column ic.
+        // trb_on: every lane carries column l % NU through the same chain and keeps g of step l / NU by a select;
+        // one store pass after the recursion writes the table and its fragment image from all lanes (a lane past
+        // N NU columns repeats slot 0's store with slot 0's values), a second the image's all-zero slots
+        constexpr bool kTrb = trb_on<TI, T>();
+        const int ic = kTrb ? l % NU : (l < NU ? l : 0);
+        const int dq = l < N * NU ? l / NU : 0;
+        double ar[NX * NX], g[NX], cap[NX];
 #pragma unroll
         for (int i = 0; i < NX * NX; ++i) ar[i] = sA[i];
 #pragma unroll
         for (int s = 0; s < NX; ++s) g[s] = sB[ti_slot<NX, NU>(0, ic) + s];
+#pragma unroll
+        for (int s = 0; s < NX; ++s) cap[s] = g[s];
         // TF: every slot's copy in the fragment image (tf_pair), the zero slot included
         double* sGf = sm + L.Gf;
         auto put_frag = [&](int d, bool zero) __attribute__((always_inline)) {
-            if constexpr (tf_on<TI, T>()) {
+            if constexpr (tf_on<TI, T>() && !kTrb) {
                 if (l < NU) {
                     double* gp = sGf + tf_slot<NU>(d, ic);
                     gp[0] = zero ? 0.0 : g[0];
@@ -940,28 +1023,53 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             }
 #pragma unroll
             for (int s = 0; s < NX; ++s) g[s] = gn[s];
-            if (l < NU) {
+            if constexpr (kTrb) {
 #pragma unroll
-                for (int s = 0; s < NX; ++s) sB[ti_slot<NX, NU>(d, ic) + s] = g[s];
+                for (int s = 0; s < NX; ++s) cap[s] = (d == dq) ? g[s] : cap[s];
+            } else {
+                if (l < NU) {
+#pragma unroll
+                    for (int s = 0; s < NX; ++s) sB[ti_slot<NX, NU>(d, ic) + s] = g[s];
+                }
+                put_frag(d, false);
             }
-            put_frag(d, false);
+        }
+        if constexpr (kTrb) {
+            static_assert(NX == 4 && 16 % NU == 0, "the fragment image's pairs; its leading slots fill a row");
+#pragma unroll
+            for (int s = 0; s < NX; ++s) sB[ti_slot<NX, NU>(dq, ic) + s] = cap[s];
+            if constexpr (tf_on<TI, T>()) {
+                double* gp = sGf + tf_slot<NU>(dq, ic);
+                gp[0] = cap[0];
+                gp[1] = cap[1];
+                gp[2] = cap[2];
+                gp[3] = 0.0;
+                gp[4] = cap[3];
+                gp[5] = 0.0;
+                // slots -tf_lead .. -1 and slot N: 16 columns, one per lane of a row (the rows repeat them)
+                const int j = l & 15;
+                double* zp = sGf + tf_slot<NU>(j < tf_lead<NU>() * NU ? -1 - j / NU : N, j % NU);
+#pragma unroll
+                for (int i = 0; i < kTfG; ++i) zp[i] = 0.0;
+            }
         }
         wsync();
     }
     constexpr bool kSeg = seg_on<T, NX, NU, LS>();
+    constexpr bool kTr = tr_on<TI, T>();
     double* sPhi = sm + L.Phi;
     // x_{k+1} = A_k x_k + B_k u_k, by segments where the instantiation has them.  The lane index is
     // an argument: inside the iteration loop it is the loop's own (opaque) copy, so the segment
     // bounds derived from it are recomputed there instead of hoisted and held across the loop
     auto fwd = [&](int lv, const double* x0v, const double* Uv, double* Xv) __attribute__((always_inline)) {
-        if constexpr (kSeg) fwd3seg<NX, NU, TI>(lv, N, sA, sB, x0v, Uv, Xv, sPhi);
-        else fwd3<NX, NU, LS, TI>(lv, N, sA, sB, x0v, Uv, Xv);
+        if constexpr (kSeg) fwd3seg<NX, NU, TI, kTr>(lv, N, sA, sB, x0v, Uv, Xv, sPhi);
+        else fwd3<NX, NU, LS, TI, kTr>(lv, N, sA, sB, x0v, Uv, Xv);
     };
     double* sPst = sm + L.Pst;
     if constexpr (kSeg) {
         if (wvi == 0) {
-            phi_build<NX>(l, N, sA, sPhi);
-            psi_build<NX>(l, N, sA, sPst);
+            phi_build<NX, trb_on<TI, T>()>(l, N, sA, sPhi);
+            psi_build<NX, trb_on<TI, T>()>(l, N, sA, sPst);
         }
         wsync();
     }
@@ -1141,7 +1249,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
         STAMP(0);
         // psi over yb (-> gradient) and over dX (-> rd): two 30-stage chains side by side on the rows of
         // the wave (segmenting both on the quads of the rows measured slower: 3.7k -> 3.9k clk)
-        psi3<NX, LS>(l, N, sA, yb, dX);
+        psi3<NX, LS, kTr>(l, N, sA, yb, dX);
         wsync();
         STAMP(1);
         double gs_l = 1.0, nrd_l = 0.0, nrs_l = 0.0, nrp_l = 0.0, mu_l = 0.0;
@@ -2057,8 +2165,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             if (l < NX) yb[l] = 0.0;
             wsync();
             STAMP(8);
-            if constexpr (kSeg) psi3seg<NX>(l, N, sA, yb, sPst);
-            else psi3<NX, LS>(l, N, sA, yb, yb);
+            if constexpr (kSeg) psi3seg<NX, kTr>(l, N, sA, yb, sPst);
+            else psi3<NX, LS, kTr>(l, N, sA, yb, yb);
             wsync();
             STAMP(9);
             if (!lo && own) {
