@@ -221,6 +221,21 @@ constexpr bool kTiRegsBuild = true;
 #endif
 template <bool TI, int T>
 __host__ __device__ constexpr bool trb_on() { return tr_on<TI, T>() && kTiRegsBuild; }
+//  pivot_acc_on  the factorisation's 16 T pivot tests `!(d_jj > 0)` are each taken where the pivot is formed, as a
+//              lane-mask compare or-ed into a running scalar pair, and the verdict is that pair's test: a scalar
+//              branch.  Written as a per-lane flag beside the pivot, the tests were all evaluated after the last
+//              block instead: every pivot was parked (accumulator registers, VGPRs) through the Cholesky, the
+//              T = 4 code rebuilt the flag from 64 mask pairs, some of them spilled, and the breakdown exit was
+//              an EXEC region the rest of the iteration ran behind.  Same predicate (a NaN pivot is a breakdown,
+//              +inf is not); no floating-point operation changes.
+// -DCMPC_NO_PIVOT_ACC restores the per-lane flag (A/B builds).
+#ifdef CMPC_NO_PIVOT_ACC
+constexpr bool kPivotAcc = false;
+#else
+constexpr bool kPivotAcc = true;
+#endif
+template <int T>
+__host__ __device__ constexpr bool pivot_acc_on() { return kPivotAcc; }
 constexpr int kTfW = 8;  // doubles per stage of the weights' fragment image
 constexpr int kTfG = 6;  // doubles per column of the table's fragment image
 template <int NU>
@@ -1955,6 +1970,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
 
         // ================= blocked Cholesky in the accumulator registers =================
         bool chol_ok = true;
+        // pivot_acc_on: the lanes that met a non-positive or NaN pivot, and the last pivot's compare (wave_ops.h)
+        unsigned long long piv_bad = 0, piv_pend = 0;
         // diagonal blocks L_JJ -> L_JJ^{-1} in place (LDS, lower triangle; zeros above): row q of the
         // wave inverts block q, lane (q, j) forms column j by forward substitution.  Done once per
         // factorisation, it turns every in-block substitution of the four triangular solves per
@@ -2027,7 +2044,8 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 static_for<0, 16>([&](auto jc) __attribute__((always_inline)) {
                     constexpr int j = decltype(jc)::value;
                     const double djj = bcast16<j>(j == 0 ? rw[0] : dn);
-                    if (!(djj > 0.0)) chol_ok = false;
+                    if constexpr (pivot_acc_on<T>()) acc_nonpositive(piv_bad, piv_pend, djj);
+                    else if (!(djj > 0.0)) chol_ok = false;
                     const double y = rsqrt_d(djj);
                     const double lj = rw[j] * y;
                     rw[j] = lj;
@@ -2042,8 +2060,11 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
                 });
             }
             if (l < 16) {
+                // (pivot_acc_on: cc <= l as the panel solve's i16 > cc - 1, l = l & 15 here: the two selects then
+                // share one set of lane masks instead of holding, and spilling, one each)
+                const int lr = pivot_acc_on<T>() ? (l & 15) : l;
 #pragma unroll
-                for (int cc = 0; cc < 16; ++cc) S0[l * 17 + cc] = (cc <= l) ? rw[cc] : 0.0;
+                for (int cc = 0; cc < 16; ++cc) S0[l * 17 + cc] = (cc <= lr) ? rw[cc] : 0.0;
             }
             wsync();
             STAMP(6);
@@ -2102,6 +2123,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64, 1) void mpc_ipm3_kernel(const MpcCon
             STAMP(7);
         }
         }
+        if constexpr (pivot_acc_on<T>()) chol_ok = (piv_bad | piv_pend) == 0;
         // ================= predictor / corrector =================
         double sig_c = 0.0, alpha = 0.0;
         // the right-hand side of a pass: rho (pass 1: Mehrotra's second-order term from the predictor still

@@ -150,6 +150,16 @@ __device__ __forceinline__ double fnma_bcast16s(double a, double x, double c) {
     }
 }
 
+// Running test "some d was not > 0.0" (a NaN counts, +inf does not) over a sequence of calls, as lane masks in
+// two scalar pairs: a call or-s the previous call's compare (pend) into m, then compares its own d into pend;
+// m | pend is the verdict after the last call.  One compare and one scalar or per call, chained through m and
+// pend, so the compiler can neither park d for a later compare nor keep one mask per call and reassociate the
+// ors (it does both with the intrinsic compare or a per-lane flag); the or reads a mask written a whole call
+// earlier, not the compare beside it, which it would have to wait for
+__device__ __forceinline__ void acc_nonpositive(unsigned long long& m, unsigned long long& pend, double d) {
+    asm("s_or_b64 %0, %0, %1\n\tv_cmp_nlt_f64_e64 %1, 0, %2" : "+s"(m), "+s"(pend) : "v"(d) : "scc");
+}
+
 // 1/sqrt(x) to full double precision: hardware estimate + two Newton steps.
 __device__ __forceinline__ double rsqrt_d(double x) {
     double y = __builtin_amdgcn_rsq(x);
