@@ -238,6 +238,16 @@ class cmpc_lin_rounds_table_init(ct.Structure):
                 ("C", _DP), ("h", _DP), ("x0", _DP), ("u_prev", _DP), ("nbr", _IP), ("traj", _DP)]
 
 
+class cmpc_consensus_opts(ct.Structure):   # the stopping rule of a consensus step (scenarios.consensus_stop)
+    _fields_ = [("min_rounds", ct.c_int), ("need", ct.c_int), ("max_rounds", ct.c_int), ("atol", ct.c_double),
+                ("rtol", ct.c_double)]
+
+
+class cmpc_consensus_out(ct.Structure):    # host pointers, any may be None
+    _fields_ = [("inner_rounds", _IP), ("agreed", _IP), ("not_close", _IP), ("cap", ct.c_int), ("close", _IP),
+                ("delta", _DP)]
+
+
 class cmpc_log_dims(ct.Structure):
     _fields_ = [(k, ct.c_int) for k in ("batch", "nx", "nu", "ns", "N", "look_col")]
 
@@ -423,6 +433,10 @@ SIGNATURES = {
     "cmpc_lin_rounds_get_time": (ct.c_int, [ct.c_void_p, _IP]),
     "cmpc_lin_rounds_set_time": (ct.c_int, [ct.c_void_p, ct.c_int]),
     "cmpc_lin_rounds_table_write": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(cmpc_lin_table)]),
+    "cmpc_lin_publish_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin_params), ct.POINTER(cmpc_lin_dims), ct.c_int,
+                                        ct.c_int, _DP, _DP, ct.c_double, ct.c_double, _DP, _IP, _DP, _IP, ct.c_void_p]),
+    "cmpc_lin_rounds_step_consensus": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(cmpc_consensus_opts), _IP, _IP]),
+    "cmpc_lin_rounds_consensus_read": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_consensus_out)]),
 }
 
 CMPC_COMM_ID_BYTES = 128

@@ -229,6 +229,39 @@ def lin_advance_dev(prm, z, nx, nu, ns, N, x0, u_prev, traj_local, ctx=None, str
                                            ct.c_void_p(getattr(stream, "cuda_stream", stream))))
 
 
+def lin_publish_dev(prm, z, nx, nu, ns, N, traj_all, traj_local, atol=0.01, rtol=1e-5, self_offset=0, close=None,
+                    delta=None, not_close=None, ctx=None, stream=None):
+    """An inner round's publication on the device — one launch of cmpc_lin_publish_dev on ``stream`` (default:
+    torch's current one), no host synchronisation; the rule is ``scenarios.lin_publish``'s, bit for bit.
+    ``traj_local`` (B, N+1, 2) <- the positions predicted by ``z`` (B, nz, reference layout), or the agent's row of
+    ``traj_all`` (n_total, N+1, 2) again when its z is not finite; ``close`` (B,) int32, ``delta`` (B,) fp64 and
+    ``not_close`` (1,) int32 are optional: the allclose verdict against that row, the largest move, and the count
+    of agents that are not close ADDED to ``not_close`` (zero it first).  Contiguous CUDA tensors; ``traj_local``
+    must not alias ``traj_all``."""
+    import torch
+
+    B = int(z.shape[0])
+    if z.dim() != 2 or z.shape[1] != (nx + ns) * (N + 1) + 2 * nu * N or traj_all.dim() != 3 or \
+            tuple(traj_all.shape[1:]) != (N + 1, 2) or tuple(traj_local.shape) != (B, N + 1, 2) or \
+            self_offset < 0 or self_offset + B > traj_all.shape[0]:
+        raise ValueError("z (B, (nx+ns)(N+1) + 2 nu N), traj_all (n_total >= self_offset + B, N+1, 2), traj_local "
+                         "(B, N+1, 2)")
+    for name, t, dt, shp in (("close", close, torch.int32, (B,)), ("delta", delta, torch.float64, (B,)),
+                             ("not_close", not_close, torch.int32, (1,))):
+        if t is not None and (t.device != z.device or t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous {shp} {dt} tensor on {z.device}")
+    if B == 0:   # empty tensors have no address to hand over; the entry point launches nothing either
+        return
+    ctx = ctx or L.default_context(z.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(z.device)
+    dims = L.cmpc_lin_dims(B, int(N), 0, int(self_offset), int(nx), 0)
+    ctx.check(ctx.lib.cmpc_lin_publish_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), int(ns), int(nu), _tptr(z),
+                                           _tptr(traj_all), float(atol), float(rtol), _tptr(traj_local), _tptr(close),
+                                           _tptr(delta), _tptr(not_close),
+                                           ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+
+
 def lin_round_dev(prm, own, nbr, traj_all, shared, dev, out, traj_local, self_offset=0, opts=None, ctx=None,
                   stream=None):
     """One round of the family on the device (cmpc_lin_round_dev): the builder into ``dev["qlin" | "C" | "h"]``,
@@ -930,6 +963,31 @@ class LinRoundsHandle(_RoundsHandle):
         done = ct.c_int()
         self._call("step", int(rounds), ct.byref(done))
         return done.value
+
+    def step_consensus(self, steps=1, min_rounds=3, need=2, max_rounds=12, atol=0.01, rtol=1e-5):
+        """Runs ``steps`` consensus steps (cmpc_lin_rounds_step_consensus): each repeats build, solve, publish and
+        exchange at the handle's state (and table time) until the published positions agree — the rule of
+        ``scenarios.consensus_stop`` on the node-wide counts of ``scenarios.lin_publish`` — and then advances.  A
+        consensus step is one round for ``history``, ``log`` and ``time``; ``max_rounds=1`` is ``step(1)``.  The
+        defaults are the reference's loop (NL_EU_N_main.py:102-162).  Returns (steps done, inner rounds run)."""
+        co = L.cmpc_consensus_opts(int(min_rounds), int(need), int(max_rounds), float(atol), float(rtol))
+        done, inner = ct.c_int(), ct.c_int()
+        self._call("step_consensus", int(steps), ct.byref(co), ct.byref(done), ct.byref(inner))
+        return done.value, inner.value
+
+    def consensus(self):
+        """The latest consensus step: dict of inner_rounds, agreed (bool), not_close (inner_rounds,) int32 — the
+        node-wide count of agents whose published positions moved, after each inner round (entry 0: against the
+        previous step's plan) — and this rank's close (B,) int32 and delta (B,) of the last inner round."""
+        n, agreed = ct.c_int(), ct.c_int()
+        o = L.cmpc_consensus_out(ct.pointer(n), ct.pointer(agreed), None, 0, None, None)
+        self._call("consensus_read", ct.byref(o))
+        r = dict(inner_rounds=n.value, agreed=bool(agreed.value), not_close=np.zeros(n.value, np.int32),
+                 close=np.zeros(self.B, np.int32), delta=np.zeros(self.B))
+        o = L.cmpc_consensus_out(None, None, L.iptr(r["not_close"]) if n.value else None, n.value, L.iptr(r["close"]),
+                                 L.dptr(r["delta"]))
+        self._call("consensus_read", ct.byref(o))
+        return r
 
     def read(self):
         """The latest round: dict of z, kkt, iters, status, x0, u_prev (the next round's), nbr."""

@@ -215,6 +215,53 @@ def lin_advance(prm, z, nx, nu, ns, N, x0, u_prev, traj_local):
     return x0, u_prev, traj_local
 
 
+def lin_publish(prm, z, nx, nu, ns, N, traj_all, atol=0.01, rtol=1e-5, self_offset=0):
+    """Host statement of an inner round's publication (cmpc_lin_publish_dev, include/cmpc.h), every expression
+    rounded as written.  ``z`` (B, nz) in the reference layout, ``traj_all`` (n_total, N+1, 2); the local agents are
+    rows self_offset .. self_offset + B of it (``prev``).  With new[k] = (z[k nxe + ix], z[k nxe + iy]): an agent
+    whose z holds any non-finite value publishes ``prev`` again, with close = 0 and delta = NaN; every other agent
+    publishes ``new``, close = all(|prev - new| <= atol + rtol |new|) (numpy's allclose: a NaN is never close) and
+    delta = max |prev - new| (numpy's max: NaN when any term is).  Returns (traj_local (B, N+1, 2), close (B,) int32,
+    delta (B,), not_close = the number of agents with close == 0); the arguments are left alone."""
+    z, traj_all = np.asarray(z, np.float64), np.asarray(traj_all, np.float64)
+    ix, iy, nxe, off = int(prm["ix"]), int(prm["iy"]), nx + ns, int(self_offset)
+    if z.ndim != 2 or z.shape[1] != nxe * (N + 1) + 2 * nu * N or traj_all.ndim != 3 or \
+            traj_all.shape[1:] != (N + 1, 2) or not (0 <= off and off + z.shape[0] <= traj_all.shape[0]) or \
+            not (0 <= ix < nx and 0 <= iy < nx and ix != iy) or not (atol >= 0 and rtol >= 0):
+        raise ValueError("lin_publish: z (B, (nx+ns)(N+1) + 2 nu N), traj_all (n_total >= self_offset + B, N+1, 2), "
+                         "ix != iy in [0, nx), atol, rtol >= 0")
+    B = z.shape[0]
+    prev = traj_all[off:off + B]
+    ok = np.isfinite(z).all(axis=1)
+    xi = z[:, :nxe * (N + 1)].reshape(B, N + 1, nxe)
+    new = np.stack([xi[:, :, ix], xi[:, :, iy]], axis=-1)
+    traj_local = np.where(ok[:, None, None], new, prev)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.abs(prev - traj_local).reshape(B, -1)
+        lim = (atol + rtol * np.abs(traj_local)).reshape(B, -1)
+        close = ((d <= lim).all(axis=1) & ok).astype(np.int32)
+        delta = np.where(ok, d.max(axis=1), np.nan)
+    return traj_local, close, delta, int((close == 0).sum())
+
+
+def consensus_stop(not_close, min_rounds=3, need=2, max_rounds=12):
+    """The stopping rule of a consensus step (cmpc_lin_rounds_step_consensus, include/cmpc.h) as a pure function of
+    the node-wide ``not_close`` counts of the inner rounds 1..j run so far (j = len(not_close) >= 1).  Round 1 is
+    not compared; for rounds >= 2 ``streak`` counts the consecutive rounds, ending at the current one, whose count
+    was 0; ``agreed`` turns true the first time streak >= need and stays true; the step stops after round j when
+    j >= max_rounds, or when agreed and j >= min_rounds.  Returns (stop, agreed).  ``ocd.OCDLoopState`` with
+    min_rounds = min_it_OCD + 1, need = it_conv + 1, max_rounds = max_it_OCD + 2 (the defaults are the
+    reference's)."""
+    j = len(not_close)
+    if j < 1 or min_rounds < 1 or need < 1 or max_rounds < min_rounds:
+        raise ValueError("consensus_stop: at least one round, 1 <= min_rounds <= max_rounds, need >= 1")
+    streak, agreed = 0, False
+    for c in list(not_close)[1:]:
+        streak = streak + 1 if int(c) == 0 else 0
+        agreed = agreed or streak >= need
+    return bool(j >= max_rounds or (agreed and j >= min_rounds)), bool(agreed)
+
+
 def lin_of_di(scen, rows=None):
     """A ``DIScenario`` in the linear-model family: the arguments of ``lin_rows`` (and of cmpc_lin_build_dev) that
     give the double-integrator builder's qlin, C, h bit for bit.  Position columns ix, iy = 0, 1; mo = 4 own rows

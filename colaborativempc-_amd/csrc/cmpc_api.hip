@@ -944,6 +944,24 @@ int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_l
     return CMPC_OK;
 }
 
+int cmpc_lin_publish_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+                         const double* z, const double* traj_all, double atol, double rtol, double* traj_local,
+                         int* close, double* delta, int* not_close, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!z || !traj_all || !traj_local) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    cmpc::LinConst c;
+    int rc = lin_const(ctx, prm, d, &c);
+    if (rc != CMPC_OK) return rc;
+    if (ns < 0 || ns > CMPC_MAX_NS || nu < 1 || nu > CMPC_MAX_NU)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (0 <= ns <= 4, 1 <= nu <= 4)");
+    if (!(atol >= 0.0) || !(rtol >= 0.0)) return fail(ctx, CMPC_ERR_ARG, "atol and rtol: >= 0 (not NaN)");
+    if (d->batch == 0) return CMPC_OK;
+    if ((rc = set_device(ctx)) != CMPC_OK) return rc;
+    HIP_TRY(cmpc::lin_publish_launch(c, ns, nu, atol, rtol, z, traj_all, traj_local, close, delta, not_close, d->batch,
+                                     (hipStream_t)stream));
+    return CMPC_OK;
+}
+
 // What cmpc_lin_round_dev and cmpc_lin_table_round_dev check after their own rules: the two dims structs describe
 // the same agents, and every argument rule of the solver before the first launch (cmpc_solve_mpc_batch_dev
 // repeats them).

@@ -389,6 +389,10 @@ hipError_t lin_table_build_launch(const LinConst& c, const LinTableConst& tc, co
                                   hipStream_t s);
 hipError_t lin_advance_launch(const LinConst& c, int ns, int nu, const double* z, double* x0, double* up,
                               double* traj, int batch, hipStream_t s);
+// an inner round's publication (cmpc_lin_publish_dev); close, delta, not_close may be null
+hipError_t lin_publish_launch(const LinConst& c, int ns, int nu, double atol, double rtol, const double* z,
+                              const double* traj_all, double* traj_local, int* close, double* delta, int* not_close,
+                              int batch, hipStream_t s);
 
 hipError_t selftest_mfma_launch(const double* A, const double* B, double* D, hipStream_t s);
 hipError_t selftest_fma_bcast_launch(const double* A, const double* X, const double* C, const double* one,

@@ -6,6 +6,9 @@
 //   DI:  [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 //   LIN: [cmpc_nbr_select_dev ->] cmpc_lin_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 //        (over a stage table: cmpc_lin_table_round_dev at the handle's time, which then moves on one stage)
+//   LIN, a consensus step (cmpc_lin_rounds_step_consensus): [cmpc_nbr_select_dev ->] inner rounds of
+//        cmpc_lin[_table]_build_dev -> cmpc_solve_mpc_batch_dev -> cmpc_lin_publish_dev -> exchange -> 4-byte
+//        read-back, until the published positions agree -> cmpc_lin_advance_dev
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's communicator
 // (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).  With the log on
 // (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1] into the
@@ -126,6 +129,12 @@ struct cmpc_lin_rounds : SolverRounds {
     // the stage table of cmpc_lin_rounds_create_table (T == 0: a fixed-window handle) and the next round's time
     int T = 0, mode = CMPC_TABLE_HOLD, t = 0;
     double *A_tab = nullptr, *B_tab = nullptr;  // T stages; the round gathers their window into A, B
+    // the latest consensus step (cmpc_lin_rounds_step_consensus): the last inner round's verdicts on the device,
+    // the node-wide count of every inner round and the loop's outcome on the host
+    int *close = nullptr, *not_close = nullptr;
+    double* delta = nullptr;
+    std::vector<int> trace;
+    bool agreed = false;
 };
 
 namespace {
@@ -549,7 +558,8 @@ int lin_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights
                   {h->h_own, uh}, {h->traj_all, T * row}, {h->traj_local, B * row}, {h->qlin, nq},
                   {h->C, B * N * mc * nx}, {h->h, B * N * mc}, {h->z, B * nz_mpc(h->md)}, {h->kkt, H * B},
                   {h->nbr, B * nb1}, {h->iters, H * B}, {h->status, H * B}, {h->order, B},
-                  {h->A_tab, table ? uA : 0}, {h->B_tab, table ? uB : 0}});
+                  {h->A_tab, table ? uA : 0}, {h->B_tab, table ? uB : 0}, {h->close, B}, {h->delta, B},
+                  {h->not_close, 1}});
     if (!bytes) {
         delete h;
         return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
@@ -858,6 +868,117 @@ int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
                            return cmpc_lin_round_dev(h->ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, &h->md, &h->w,
                                                      din, dout, &h->opts, h->traj_local, s);
                        });
+}
+
+// ---- consensus steps (include/cmpc.h, cmpc_lin_rounds_step_consensus) ----
+
+// One consensus step: inner rounds of build, solve, publish and exchange at the handle's state and time until the
+// stopping rule (cmpc.scenarios.consensus_stop) ends them, then the advance.  *inner: the inner rounds of a step
+// that was counted (0: it was not).  Returns at the first error; the caller synchronises.
+static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hipStream_t s, int* inner) {
+    cmpc_ctx* ctx = h->ctx;
+    *inner = 0;
+    const bool lpt = h->d.flags & CMPC_ROUNDS_LPT;
+    const int round = h->rounds_done;
+    const size_t slot = (size_t)(round % h->history) * h->d.batch;  // this step's row of the history ring
+    const cmpc_mpc_data din{h->A, h->B, h->x0, h->u_prev, h->qlin, h->C, h->h};
+    const cmpc_mpc_out dout{h->z, h->kkt + slot, h->iters + slot, h->status + slot};
+    const cmpc_lin_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->md.nx, h->mo};
+    const cmpc_lin_own own{h->qlin_own, h->C_own, h->h_own};
+    const cmpc_lin_table_dims td{h->T, h->mode};
+    const cmpc_lin_table tab{h->A_tab, h->B_tab, h->qlin_own, h->C_own, h->h_own};
+    int rc;
+    if ((rc = reselect(h, s)) != CMPC_OK) return rc;
+    HIP_TRY(log_mark(h->log, round, 0, s));
+    std::vector<int> trace;
+    bool agreed = false;
+    int streak = 0, j = 0;
+    for (;;) {
+        ++j;
+        rc = h->T ? cmpc_lin_table_build_dev(ctx, &h->prm, &rd, h->md.nu, &td, &tab, h->t, h->nbr, h->traj_all, h->A,
+                                             h->B, h->qlin, h->C, h->h, s)
+                  : cmpc_lin_build_dev(ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, h->qlin, h->C, h->h, s);
+        h->opts.order = (lpt && (round > 0 || j > 1)) ? h->order : nullptr;
+        if (rc == CMPC_OK) rc = cmpc_solve_mpc_batch_dev(ctx, &h->md, &h->w, &din, &dout, &h->opts, s);
+        if (rc != CMPC_OK) {
+            log_abandon(h->log, round);
+            return rc;
+        }
+        // the next solve's launch order, stream-ordered after this one
+        if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) return rc;
+        HIP_TRY(hipMemsetAsync(h->not_close, 0, sizeof(int), s));
+        if ((rc = cmpc_lin_publish_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->traj_all, co.atol, co.rtol,
+                                       h->traj_local, h->close, h->delta, h->not_close, s)) != CMPC_OK)
+            return rc;
+        if ((rc = exchange(h, s)) != CMPC_OK) return rc;
+        // the node's count, not this rank's: every rank must leave the loop after the same inner round (a rank
+        // that left alone would keep the others waiting in the next all-gather)
+        if (h->sharded() && (rc = cmpc_comm_sum_i32(ctx, h->not_close, 1, s)) != CMPC_OK) return rc;
+        int count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, h->not_close, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        trace.push_back(count);
+        if (j >= 2) streak = count == 0 ? streak + 1 : 0;  // round 1 compares against the previous step's plan
+        if (streak >= co.need) agreed = true;
+        if (j >= co.max_rounds || (agreed && j >= co.min_rounds)) break;
+    }
+    HIP_TRY(log_mark(h->log, round, 1, s));
+    // x0, u_prev from the final z; traj_local again, with the values the last inner round exchanged
+    if ((rc = cmpc_lin_advance_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->x0, h->u_prev, h->traj_local, s)) !=
+        CMPC_OK)
+        return rc;
+    ++h->rounds_done;
+    if (h->T) h->t = h->mode == CMPC_TABLE_PERIODIC ? (h->t + 1) % h->T : std::min(h->t + 1, h->T - 1);
+    h->trace = std::move(trace);
+    h->agreed = agreed;
+    *inner = j;
+    return log_round(h, round, h->z, h->kkt + slot, h->iters + slot, h->status + slot, s);
+}
+
+int cmpc_lin_rounds_step_consensus(cmpc_lin_rounds* h, int steps, const cmpc_consensus_opts* co, int* steps_done,
+                                   int* inner_total) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    const cmpc_consensus_opts o = co ? *co : cmpc_consensus_opts{3, 2, 12, 0.01, 1e-5};  // NL_EU_N_main.py:102-104
+    if (steps < 0) return fail(ctx, CMPC_ERR_ARG, "negative step count");
+    if (o.min_rounds < 1 || o.need < 1 || o.max_rounds < o.min_rounds)
+        return fail(ctx, CMPC_ERR_ARG, "consensus: 1 <= min_rounds <= max_rounds, need >= 1");
+    if (!(o.atol >= 0.0) || !(o.rtol >= 0.0)) return fail(ctx, CMPC_ERR_ARG, "atol and rtol: >= 0 (not NaN)");
+    if (h->host_exchange() && h->sharded())
+        return fail(ctx, CMPC_ERR_ARG, "host exchange: the exchange lies inside a consensus step");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int done = 0, total = 0, rc = CMPC_OK;
+    for (int i = 0; i < steps && rc == CMPC_OK; ++i) {
+        int inner = 0;
+        rc = consensus_step(h, o, s, &inner);
+        if (inner) ++done;
+        total += inner;
+    }
+    // one more host synchronisation, also after an error: what was queued has then finished
+    const hipError_t e = hipStreamSynchronize(s);
+    if (steps_done) *steps_done = done;
+    if (inner_total) *inner_total = total;
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(e);
+    return CMPC_OK;
+}
+
+int cmpc_lin_rounds_consensus_read(cmpc_lin_rounds* h, const cmpc_consensus_out* o) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
+    if (o->cap < 0) return fail(ctx, CMPC_ERR_ARG, "negative cap");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    if (o->close) HIP_TRY(hipMemcpyAsync(o->close, h->close, 4 * B, hipMemcpyDeviceToHost, s));
+    if (o->delta) HIP_TRY(hipMemcpyAsync(o->delta, h->delta, 8 * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (o->inner_rounds) *o->inner_rounds = (int)h->trace.size();
+    if (o->agreed) *o->agreed = h->agreed ? 1 : 0;
+    if (o->not_close) std::copy_n(h->trace.begin(), std::min((size_t)o->cap, h->trace.size()), o->not_close);
+    return CMPC_OK;
 }
 
 int cmpc_lin_rounds_get_time(cmpc_lin_rounds* h, int* t) {

@@ -57,7 +57,9 @@ extern "C" {
                                 cmpc_lin_build_dev, cmpc_lin_advance_dev, cmpc_lin_round_dev, cmpc_lin_rounds_*;
                                 CMPC_TABLE_HOLD / _PERIODIC, cmpc_lin_table_dims, cmpc_lin_table,
                                 cmpc_lin_table_build_dev, cmpc_lin_table_round_dev, cmpc_lin_rounds_table_init,
-                                cmpc_lin_rounds_create_table, cmpc_lin_rounds_get_time / _set_time / _table_write */
+                                cmpc_lin_rounds_create_table, cmpc_lin_rounds_get_time / _set_time / _table_write;
+                                cmpc_lin_publish_dev, cmpc_consensus_opts, cmpc_consensus_out,
+                                cmpc_lin_rounds_step_consensus, cmpc_lin_rounds_consensus_read */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -1099,6 +1101,85 @@ int cmpc_lin_rounds_create_table(cmpc_ctx* ctx, const cmpc_lin_params* prm, cons
 int cmpc_lin_rounds_get_time(cmpc_lin_rounds* h, int* t);
 int cmpc_lin_rounds_set_time(cmpc_lin_rounds* h, int t);
 int cmpc_lin_rounds_table_write(cmpc_lin_rounds* h, int first_row, int count, const cmpc_lin_table* host_rows);
+
+/* ------------------------------------------------------------------------
+ * Consensus steps of the family: a control step that repeats build, solve, publish and exchange at a fixed state
+ * and a fixed table time until the published positions agree, and only then advances (the inner loop of
+ * NL_EU_N_main.py:105-162 on the Jacobi round above).  A plain round cuts every agent's collision planes against
+ * plans its neighbours have already abandoned; an inner round cuts them against the plans of the round before.
+ *
+ * cmpc_lin_publish_dev: one inner round's publication and its convergence test, in one launch (one wavefront per
+ * agent, no LDS, no scratch, stream-ordered, graph-capturable).  Every expression is rounded as written
+ * (cmpc.scenarios.lin_publish is its numpy statement).  For local agent b, with g = self_offset + b,
+ * prev = traj_all[g] (traj_all: n_total x (N+1) x 2), nxe = nx + ns and
+ *   new[k] = (z[b, k nxe + ix], z[b, k nxe + iy]),  k = 0..N:
+ *   z[b] holds a non-finite value anywhere in its nz entries:
+ *     traj_local[b] <- prev, bit for bit;  close[b] = 0;  delta[b] = NaN.
+ *     (Not cmpc_lin_advance_dev's "stays as it was": after the exchange the agent's row of traj_all is unchanged
+ *     whatever traj_local held before.)
+ *   z[b] finite:
+ *     traj_local[b] <- new (copies: -0.0 stays -0.0);
+ *     close[b] = 1 exactly when |prev_e - new_e| <= atol + rtol * |new_e| for all 2(N+1) entries e — the test of
+ *       cmpc_ocd_converged_dev with x_old = prev, x_pred = new: a NaN prev_e is never close, and an infinite one
+ *       is not close under any finite atol;
+ *     delta[b] = max over e of |prev_e - new_e|, NaN when any term is NaN (numpy's max, not fmax).
+ *   *not_close += the number of agents with close == 0: one vector atomic add from one lane of each such agent, so
+ *   the caller zeroes *not_close on the stream first (the handle below does).
+ * close, delta and not_close may each be NULL: that output is skipped, the others are unchanged.  traj_local must
+ * not alias traj_all.
+ * CMPC_ERR_ARG: what cmpc_lin_advance_dev lists; a NULL traj_all; atol or rtol negative or NaN (+inf is allowed).
+ * batch == 0: CMPC_OK without a launch.
+ *
+ * The stopping rule (cmpc.scenarios.consensus_stop is its statement).  Inner rounds are numbered j = 1, 2, ...;
+ * round 1 compares against the previous step's plan and is not used (its count is recorded).  For j >= 2, streak
+ * = the number of consecutive rounds, ending at j, whose node-wide not_close was 0; agreed becomes true the first
+ * time streak >= need and stays true; the step stops after round j when j >= max_rounds, or when agreed and
+ * j >= min_rounds.  This is the reference's loop (cmpc.ocd.OCDLoopState) with min_rounds = min_it_OCD + 1, need =
+ * it_conv + 1, max_rounds = max_it_OCD + 2; a NULL cmpc_consensus_opts gives the reference's 3, 2, 12, atol 0.01,
+ * rtol 1e-5.
+ *
+ * cmpc_lin_rounds_step_consensus runs `steps` consensus steps on a handle of cmpc_lin_rounds_create or
+ * _create_table.  One step, on the context's stream:
+ *   1. CMPC_ROUNDS_RESELECT: cmpc_nbr_select_dev, once; the log's first event;
+ *   2. per inner round: cmpc_lin_build_dev (cmpc_lin_table_build_dev at the handle's time t);
+ *      cmpc_solve_mpc_batch_dev into this step's history row; with CMPC_ROUNDS_LPT cmpc_order_by_iters_dev (the
+ *      order is used from the second solve of the handle on; results do not depend on it); *not_close <- 0;
+ *      cmpc_lin_publish_dev; the exchange; sharded over the communicator, cmpc_comm_sum_i32 of the count; a 4-byte
+ *      read-back and one stream wait (as cmpc_lpv_rounds_step for its halt rule);
+ *   3. the log's second event; cmpc_lin_advance_dev from the final z (it rewrites traj_local with the values
+ *      already exchanged: no second exchange); the log row; the round count and t move on once.
+ * A consensus step is ONE round for _history, the log and t; its history row holds the last inner round's kkt,
+ * iters and status.  Plain and consensus steps may be mixed on one handle.  With max_rounds == 1 a step leaves
+ * every array a plain cmpc_lin_rounds_step(h, 1) leaves, byte for byte.  A solver error is returned unchanged and
+ * the step is not counted: x0, u_prev and t are untouched; traj_all may hold the inner rounds already exchanged.
+ * steps_done / inner_total (may be NULL): the steps completed and the inner rounds they ran.
+ * CMPC_ERR_ARG (nothing is written): a NULL handle; steps < 0; min_rounds < 1, need < 1 or max_rounds <
+ * min_rounds; atol or rtol negative or NaN; a sharded handle with CMPC_ROUNDS_HOST_EXCHANGE (the exchange lies
+ * inside the step).
+ *
+ * cmpc_lin_rounds_consensus_read (HOST pointers, any may be NULL), for the latest consensus step: its inner round
+ * count; agreed (0 / 1); not_close[j-1] = the node-wide count after inner round j, for j <= min(cap,
+ * inner_rounds) (entry 0: against the previous step's plan); this rank's close and delta (batch each) of the last
+ * inner round.  Before the first consensus step: 0 rounds, not agreed, zeros.  CMPC_ERR_ARG: a NULL handle or
+ * struct, cap < 0.
+ * ---------------------------------------------------------------------- */
+int cmpc_lin_publish_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* dims, int ns, int nu,
+                         const double* z /* batch x nz */, const double* traj_all /* n_total x (N+1) x 2 */,
+                         double atol, double rtol, double* traj_local /* batch x (N+1) x 2 */,
+                         int* close /* batch, may be NULL */, double* delta /* batch, may be NULL */,
+                         int* not_close /* device int, may be NULL */, void* hip_stream);
+
+typedef struct { int min_rounds, need, max_rounds; double atol, rtol; } cmpc_consensus_opts;   /* NULL: the defaults */
+typedef struct {    /* HOST pointers, any may be NULL */
+    int *inner_rounds, *agreed;
+    int* not_close;             /* cap entries */
+    int cap;
+    int* close;                 /* batch */
+    double* delta;              /* batch */
+} cmpc_consensus_out;
+int cmpc_lin_rounds_step_consensus(cmpc_lin_rounds* h, int steps, const cmpc_consensus_opts* co, int* steps_done,
+                                   int* inner_total);
+int cmpc_lin_rounds_consensus_read(cmpc_lin_rounds* h, const cmpc_consensus_out* host_out);
 
 
 /* ------------------------------------------------------------------------
