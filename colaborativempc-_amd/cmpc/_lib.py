@@ -437,6 +437,11 @@ SIGNATURES = {
                                         ct.c_int, _DP, _DP, ct.c_double, ct.c_double, _DP, _IP, _DP, _IP, ct.c_void_p]),
     "cmpc_lin_rounds_step_consensus": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(cmpc_consensus_opts), _IP, _IP]),
     "cmpc_lin_rounds_consensus_read": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_consensus_out)]),
+    "cmpc_lpv_publish_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_di_dims), _DP, _DP, _IP, ct.c_double, ct.c_double,
+                                        _DP, _IP, _DP, _IP, ct.c_void_p]),
+    "cmpc_lpv_rounds_step_consensus": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(cmpc_consensus_opts), _IP, _IP,
+                                                  _IP]),
+    "cmpc_lpv_rounds_consensus_read": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_consensus_out)]),
 }
 
 CMPC_COMM_ID_BYTES = 128

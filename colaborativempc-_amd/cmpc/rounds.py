@@ -262,6 +262,37 @@ def lin_publish_dev(prm, z, nx, nu, ns, N, traj_all, traj_local, atol=0.01, rtol
                                            ct.c_void_p(getattr(stream, "cuda_stream", stream))))
 
 
+def lpv_publish_dev(z, N, traj_all, traj_local, status=None, atol=0.01, rtol=1e-5, self_offset=0, close=None, delta=None,
+                    counts=None, ctx=None, stream=None):
+    """An inner round's publication of the LPV agents on the device — one launch of cmpc_lpv_publish_dev on
+    ``stream`` (default: torch's current one), no host synchronisation; the rule is ``scenarios.lpv_publish``'s, bit
+    for bit.  ``traj_local`` (B, N+1, 2) <- the X, Y predicted by ``z`` (B, 12(N+1) + 4N), or the agent's row of
+    ``traj_all`` (n_total, N+1, 2) again when its z is not finite; ``close`` (B,) int32, ``delta`` (B,) fp64 and
+    ``counts`` (2,) int32 are optional: the allclose verdict against that row, the largest move, and the counts of
+    agents that are not close / infeasible by ``status`` (B,) int32 (optional) ADDED to ``counts`` (zero it first).
+    Contiguous CUDA tensors; ``traj_local`` must not alias ``traj_all``."""
+    import torch
+
+    B = int(z.shape[0])
+    if z.dim() != 2 or z.shape[1] != 12 * (N + 1) + 4 * N or traj_all.dim() != 3 or \
+            tuple(traj_all.shape[1:]) != (N + 1, 2) or tuple(traj_local.shape) != (B, N + 1, 2) or \
+            self_offset < 0 or self_offset + B > traj_all.shape[0]:
+        raise ValueError("z (B, 12(N+1) + 4N), traj_all (n_total >= self_offset + B, N+1, 2), traj_local (B, N+1, 2)")
+    for name, t, dt, shp in (("close", close, torch.int32, (B,)), ("delta", delta, torch.float64, (B,)),
+                             ("counts", counts, torch.int32, (2,)), ("status", status, torch.int32, (B,))):
+        if t is not None and (t.device != z.device or t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous {shp} {dt} tensor on {z.device}")
+    if B == 0:   # empty tensors have no address to hand over; the entry point launches nothing either
+        return
+    ctx = ctx or L.default_context(z.device.index)
+    if stream is None:
+        stream = torch.cuda.current_stream(z.device)
+    dims = L.cmpc_di_dims(B, int(N), 0, int(self_offset))
+    ctx.check(ctx.lib.cmpc_lpv_publish_dev(ctx.h, ct.byref(dims), _tptr(z), _tptr(traj_all), _tptr(status), float(atol),
+                                           float(rtol), _tptr(traj_local), _tptr(close), _tptr(delta), _tptr(counts),
+                                           ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+
+
 def lin_round_dev(prm, own, nbr, traj_all, shared, dev, out, traj_local, self_offset=0, opts=None, ctx=None,
                   stream=None):
     """One round of the family on the device (cmpc_lin_round_dev): the builder into ``dev["qlin" | "C" | "h"]``,
@@ -457,6 +488,21 @@ class _RoundsHandle:
             self.close()
         except Exception:
             pass
+
+    def consensus(self):
+        """The latest consensus step (the handles that have ``step_consensus``): dict of inner_rounds, agreed (bool),
+        not_close (inner_rounds,) int32 — the node-wide count of agents whose published positions moved, after each
+        inner round (entry 0: against the previous step's plan) — and this rank's close (B,) int32 and delta (B,) of
+        the last inner round."""
+        n, agreed = ct.c_int(), ct.c_int()
+        o = L.cmpc_consensus_out(ct.pointer(n), ct.pointer(agreed), None, 0, None, None)
+        self._call("consensus_read", ct.byref(o))
+        r = dict(inner_rounds=n.value, agreed=bool(agreed.value), not_close=np.zeros(n.value, np.int32),
+                 close=np.zeros(self.B, np.int32), delta=np.zeros(self.B))
+        o = L.cmpc_consensus_out(None, None, L.iptr(r["not_close"]) if n.value else None, n.value, L.iptr(r["close"]),
+                                 L.dptr(r["delta"]))
+        self._call("consensus_read", ct.byref(o))
+        return r
 
     def log_range(self):
         """(first, count): the rounds the log ring holds now, counted from create."""
@@ -711,6 +757,12 @@ class LPVRounds(_TorchRounds):
         self.rdims = L.cmpc_di_dims(self.B, N, self.nb, self.off)
         # agents of the latest round the reference calls infeasible (status not in {1, 2, -2})
         self.n_infeasible = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        # the latest consensus step (step_consensus): the last inner round's verdicts and its two counts (not close,
+        # infeasible) on the device, the node-wide not-close count of every inner round and the loop's outcome
+        self.close = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        self.delta = torch.zeros(self.B, dtype=torch.float64, device=self.dev)
+        self.counts = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        self.trace, self.agreed = [], False
 
     def gather(self):
         lib = self.ctx.lib
@@ -776,19 +828,64 @@ class LPVRounds(_TorchRounds):
         sharded).  The reference's loop quits for every agent at once (LPV_HP_N_main.py:102-111):
         each rank takes the halt decision on the node's count, so no rank breaks out of the loop
         while the others wait for it in the next round's all-gather."""
+        return self._node_sum(self.n_infeasible)[0]
+
+    def _node_sum(self, counts):
+        """The int32 device counters ``counts`` summed over every rank, as a list of ints (synchronises; collective
+        when sharded)."""
         if self.world == 1:
-            return self.infeasible()
+            return counts.tolist()
+        cnt = counts.clone()
         if self.comm is not None:   # libcmpc's RCCL communicator (cmpc_comm_sum_i32)
-            cnt = self.n_infeasible.clone()
             self.comm.sum_i32(cnt, self.torch.cuda.current_stream(self.dev))
-            return int(cnt.item())
+            return cnt.tolist()
         import torch.distributed as dist
 
-        cnt = self.n_infeasible.clone()
         if dist.get_backend(self.group) == "gloo":   # gloo reduces host tensors
             cnt = cnt.cpu()
         dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=self.group)
-        return int(cnt.item())
+        return cnt.tolist()
+
+    def publish(self, atol=0.01, rtol=1e-5):
+        """An inner round's publication (``lpv_publish_dev``): ``traj_local`` <- the predicted X, Y, ``close`` /
+        ``delta`` against this rank's rows of the exchange buffer, ``counts`` <- this rank's (not close, infeasible).
+        Nothing else moves: x0, x_last, u_last, u_old stay the step's."""
+        self.counts.zero_()
+        lpv_publish_dev(self.z, self.N, self.traj_all, self.traj_local, status=self.status, atol=atol, rtol=rtol,
+                        self_offset=self.off, close=self.close, delta=self.delta, counts=self.counts, ctx=self.ctx)
+
+    def step_consensus(self, min_rounds=3, need=2, max_rounds=12, atol=0.01, rtol=1e-5, halt=True):
+        """One consensus step (what cmpc_lpv_rounds_step_consensus runs): gather, solve, publish and exchange are
+        repeated at the step's state AND linearisation (x0, x_last, u_last, u_old: every inner round linearises
+        about the previous step's prediction, as a plain round does; only the planes and the coverage weights are
+        re-cut against the newly published positions) until the published positions agree — the rule of
+        ``scenarios.consensus_stop`` on the node-wide counts — and then advances once.  An infeasible agent ends the
+        inner loop after its round when ``halt``, and InfeasibleRound is raised after the step has completed, as
+        ``step()`` does.  One host synchronisation per inner round.  Leaves ``trace`` (the node-wide not-close count
+        after each inner round), ``agreed``, ``close`` and ``delta``; returns (inner rounds, agreed)."""
+        from .scenarios import consensus_stop
+
+        if min_rounds < 1 or need < 1 or max_rounds < min_rounds or not (atol >= 0 and rtol >= 0):
+            raise ValueError("step_consensus: 1 <= min_rounds <= max_rounds, need >= 1, atol, rtol >= 0")
+        if self.reselect > 0 and self.nb and self.rounds_done % self.reselect == 0:
+            self.select_neighbours()
+        self.rounds_done += 1
+        trace = []
+        while True:
+            self.gather()
+            self.solve()
+            self.publish(atol, rtol)
+            self.exchange()
+            not_close, bad = self._node_sum(self.counts)
+            trace.append(not_close)
+            stop, agreed = consensus_stop(trace, min_rounds, need, max_rounds)
+            if stop or (halt and bad):
+                break
+        self.advance()   # traj_local again, with the values the last inner round exchanged: no second exchange
+        self.trace, self.agreed = trace, agreed
+        if halt and bad:
+            raise InfeasibleRound(bad)
+        return len(trace), agreed
 
 
 class InfeasibleRound(RuntimeError):
@@ -835,6 +932,18 @@ class LPVRoundsHandle(_RoundsHandle):
         done, bad = ct.c_int(), ct.c_int()
         self._call("step", int(rounds), ct.byref(done), ct.byref(bad))
         return done.value, bad.value
+
+    def step_consensus(self, steps=1, min_rounds=3, need=2, max_rounds=12, atol=0.01, rtol=1e-5):
+        """Runs up to ``steps`` consensus steps (cmpc_lpv_rounds_step_consensus), each what
+        ``LPVRounds.step_consensus`` runs: gather, solve, publish and exchange repeated at the handle's state and
+        linearisation until the published positions agree, then one advance.  A consensus step is one round for
+        ``log``; ``max_rounds=1`` is ``step(1)``.  With ``halt`` (the default at create) an infeasible agent ends its
+        step's inner loop and the call.  Returns (steps done, inner rounds run, infeasible agents of the last inner
+        round); ``consensus()`` has the trace."""
+        co = L.cmpc_consensus_opts(int(min_rounds), int(need), int(max_rounds), float(atol), float(rtol))
+        done, inner, bad = ct.c_int(), ct.c_int(), ct.c_int()
+        self._call("step_consensus", int(steps), ct.byref(co), ct.byref(done), ct.byref(inner), ct.byref(bad))
+        return done.value, inner.value, bad.value
 
     def read(self):
         nz = 12 * (self.N + 1) + 4 * self.N
@@ -974,20 +1083,6 @@ class LinRoundsHandle(_RoundsHandle):
         done, inner = ct.c_int(), ct.c_int()
         self._call("step_consensus", int(steps), ct.byref(co), ct.byref(done), ct.byref(inner))
         return done.value, inner.value
-
-    def consensus(self):
-        """The latest consensus step: dict of inner_rounds, agreed (bool), not_close (inner_rounds,) int32 — the
-        node-wide count of agents whose published positions moved, after each inner round (entry 0: against the
-        previous step's plan) — and this rank's close (B,) int32 and delta (B,) of the last inner round."""
-        n, agreed = ct.c_int(), ct.c_int()
-        o = L.cmpc_consensus_out(ct.pointer(n), ct.pointer(agreed), None, 0, None, None)
-        self._call("consensus_read", ct.byref(o))
-        r = dict(inner_rounds=n.value, agreed=bool(agreed.value), not_close=np.zeros(n.value, np.int32),
-                 close=np.zeros(self.B, np.int32), delta=np.zeros(self.B))
-        o = L.cmpc_consensus_out(None, None, L.iptr(r["not_close"]) if n.value else None, n.value, L.iptr(r["close"]),
-                                 L.dptr(r["delta"]))
-        self._call("consensus_read", ct.byref(o))
-        return r
 
     def read(self):
         """The latest round: dict of z, kkt, iters, status, x0, u_prev (the next round's), nbr."""

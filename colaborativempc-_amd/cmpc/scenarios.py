@@ -262,6 +262,27 @@ def consensus_stop(not_close, min_rounds=3, need=2, max_rounds=12):
     return bool(j >= max_rounds or (agreed and j >= min_rounds)), bool(agreed)
 
 
+LPV_PUBLISH = dict(prm=dict(ix=7, iy=8), nx=9, nu=2, ns=3)   # the LPV agents' z layout in lin_publish's terms
+
+
+def lpv_publish(z, N, traj_all, status=None, atol=0.01, rtol=1e-5, self_offset=0):
+    """Host statement of an inner round's publication on the LPV handles (cmpc_lpv_publish_dev, include/cmpc.h):
+    ``lin_publish`` on the LPV layout (positions in state columns 7, 8 of 9 states + 3 slacks per stage, 2 inputs:
+    nz = 12(N+1) + 4N), plus the reference's feasibility rule on ``status`` (B,): an agent whose status is not in
+    {1, 2, -2} is infeasible (LPV_Planner.py:243-249, what cmpc_lpv_advance_dev counts).  Returns (traj_local
+    (B, N+1, 2), close (B,) int32, delta (B,), not_close, infeasible); infeasible is 0 when ``status`` is None."""
+    c = LPV_PUBLISH
+    traj_local, close, delta, not_close = lin_publish(c["prm"], z, c["nx"], c["nu"], c["ns"], N, traj_all, atol=atol,
+                                                      rtol=rtol, self_offset=self_offset)
+    infeasible = 0
+    if status is not None:
+        status = np.asarray(status)
+        if status.shape != (close.shape[0],):
+            raise ValueError("lpv_publish: status (B,)")
+        infeasible = int((~np.isin(status, (1, 2, -2))).sum())
+    return traj_local, close, delta, not_close, infeasible
+
+
 def lin_of_di(scen, rows=None):
     """A ``DIScenario`` in the linear-model family: the arguments of ``lin_rows`` (and of cmpc_lin_build_dev) that
     give the double-integrator builder's qlin, C, h bit for bit.  Position columns ix, iy = 0, 1; mo = 4 own rows

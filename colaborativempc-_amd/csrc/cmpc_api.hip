@@ -747,6 +747,21 @@ int cmpc_lpv_advance_dev(cmpc_ctx* ctx, const cmpc_di_dims* d, const double* z, 
     return CMPC_OK;
 }
 
+int cmpc_lpv_publish_dev(cmpc_ctx* ctx, const cmpc_di_dims* d, const double* z, const double* traj_all,
+                         const int* status, double atol, double rtol, double* traj_local, int* close, double* delta,
+                         int* counts, void* stream) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!d || !z || !traj_all || !traj_local) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    if (d->N < 1 || d->batch < 0 || d->self_offset < 0) return fail(ctx, CMPC_ERR_ARG, "bad dimensions");
+    if (!(atol >= 0.0) || !(rtol >= 0.0)) return fail(ctx, CMPC_ERR_ARG, "atol and rtol: >= 0 (not NaN)");
+    if (d->batch == 0) return CMPC_OK;
+    int rc = set_device(ctx);
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(cmpc::lpv_publish_launch(d->N, d->self_offset, atol, rtol, z, traj_all, traj_local, status, close, delta,
+                                     counts, d->batch, (hipStream_t)stream));
+    return CMPC_OK;
+}
+
 int cmpc_lpv_build_dev(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc_track* tr, const cmpc_lpv_dims* d,
                        const cmpc_lpv_data* in, const cmpc_lpv_build_out* out, void* stream) {
     if (!ctx || !in || !out || !d) return fail(ctx, CMPC_ERR_ARG, "null argument");

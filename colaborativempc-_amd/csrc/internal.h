@@ -306,6 +306,10 @@ hipError_t lpv_gather_launch(int N, int nb, int self_offset, const int* nbr, con
 hipError_t lpv_advance_launch(int N, const double* z, double* x0, double* x_last, double* u_last, double* u_old,
                               double* traj_local, int batch, hipStream_t s, const int* status = nullptr,
                               int* infeasible = nullptr);
+// an inner round's publication (cmpc_lpv_publish_dev); status, close, delta, counts (int[2]) may be null
+hipError_t lpv_publish_launch(int N, int self_offset, double atol, double rtol, const double* z, const double* traj_all,
+                              double* traj_local, const int* status, int* close, double* delta, int* counts, int batch,
+                              hipStream_t s);
 
 // Neighbour selection (nbr_select.hip): the nb nearest other agents of every local agent by
 // (min over stages k0..k1 of the squared distance, index), nearest first; dist2 may be null

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "internal.h"
+#include "publish.h"
 #include "wave_ops.h"
 
 namespace cmpc {
@@ -162,40 +163,18 @@ __global__ __launch_bounds__(kWave) void lin_advance_kernel(const LinConst c, in
 
 // An inner round's publication (include/cmpc.h, cmpc_lin_publish_dev): traj_local <- predicted (z[ix], z[iy]) and
 // the allclose test of it against the agent's row of the exchange buffer; an agent with a non-finite z publishes
-// that row again and is never close.  One lane per position entry; the verdict and the largest move go through
-// the wave (nmax keeps a NaN, as numpy's max does), and lane 0 writes them and counts the agent.
+// that row again and is never close.  The rule is publish_agent's (publish.h), shared with the LPV family's kernel.
 __global__ __launch_bounds__(kWave) void lin_publish_kernel(const LinConst c, int ns, int nu, double atol, double rtol,
                                                             const double* __restrict__ z,
                                                             const double* __restrict__ traj_all,
                                                             double* __restrict__ traj_local, int* close, double* delta,
                                                             int* not_close) {
-#pragma clang fp contract(off)
     const int b = blockIdx.x;
     const int N = c.N, nxe = c.nx + ns, per = 2 * (N + 1);
     const size_t nz = (size_t)nxe * (N + 1) + 2 * (size_t)nu * N;
-    const double* zb = z + (size_t)b * nz;
-    const double* prev = traj_all + (size_t)(c.self_offset + b) * per;
-    double* out = traj_local + (size_t)b * per;
-    bool bad = false;
-    for (size_t i = threadIdx.x; i < nz; i += kWave) bad |= !isfinite(zb[i]);
-    bad = __any(bad);  // (the workgroup is one wavefront)
-    bool far = bad;
-    double dm = 0.0;
-    for (int i = threadIdx.x; i < per; i += kWave) {
-        const double p = prev[i];
-        const double v = bad ? p : zb[(size_t)(i >> 1) * nxe + ((i & 1) ? c.iy : c.ix)];
-        out[i] = v;
-        const double d = fabs(p - v), lim = atol + rtol * fabs(v);
-        far |= !(d <= lim);  // NaN is never close (numpy equal_nan=False)
-        dm = nmax(d, dm);
-    }
-    far = __any(far);
-    dm = wave_max(dm);  // (every lane is active here)
-    if (threadIdx.x == 0) {
-        if (close) close[b] = far ? 0 : 1;
-        if (delta) delta[b] = bad ? __builtin_nan("") : dm;
-        if (not_close && far) atomicAdd(not_close, 1);
-    }
+    publish_agent(z + (size_t)b * nz, nz, nxe, c.ix, c.iy, per, traj_all + (size_t)(c.self_offset + b) * per,
+                  traj_local + (size_t)b * per, atol, rtol, close ? close + b : nullptr, delta ? delta + b : nullptr,
+                  not_close);
 }
 
 }  // namespace

@@ -3,6 +3,9 @@
 // A handle owns this rank's agent state and the node-global exchange buffer in one device allocation; a round
 // chains the C-ABI device entry points on the context's stream:
 //   LPV: [cmpc_nbr_select_dev ->] cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_advance_dev -> exchange
+//   LPV, a consensus step (cmpc_lpv_rounds_step_consensus): [cmpc_nbr_select_dev ->] inner rounds of
+//        cmpc_lpv_gather_dev -> cmpc_solve_lpv_batch_dev -> cmpc_lpv_publish_dev -> exchange -> 8-byte read-back at a
+//        fixed state and linearisation, until the published positions agree -> cmpc_lpv_advance_dev
 //   DI:  [cmpc_nbr_select_dev ->] cmpc_di_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 //   LIN: [cmpc_nbr_select_dev ->] cmpc_lin_round_dev -> [cmpc_order_by_iters_dev ->] exchange
 //        (over a stage table: cmpc_lin_table_round_dev at the handle's time, which then moves on one stage)
@@ -85,6 +88,13 @@ struct RoundsCore {
     char* mem = nullptr;       // the device block of everything below and of the family's own arrays
     double *traj_all = nullptr, *traj_local = nullptr;
     int* nbr = nullptr;
+    // the latest consensus step (cmpc_lin_rounds_step_consensus, cmpc_lpv_rounds_step_consensus): the last inner
+    // round's verdicts and its two counts (not close; LPV: infeasible) on the device, the node-wide not-close count
+    // of every inner round and the loop's outcome on the host
+    int *close = nullptr, *counts = nullptr;
+    double* delta = nullptr;
+    std::vector<int> trace;
+    bool agreed = false;
 
     bool sharded() const { return d.batch != d.n_total; }
     bool host_exchange() const { return d.flags & CMPC_ROUNDS_HOST_EXCHANGE; }
@@ -129,12 +139,6 @@ struct cmpc_lin_rounds : SolverRounds {
     // the stage table of cmpc_lin_rounds_create_table (T == 0: a fixed-window handle) and the next round's time
     int T = 0, mode = CMPC_TABLE_HOLD, t = 0;
     double *A_tab = nullptr, *B_tab = nullptr;  // T stages; the round gathers their window into A, B
-    // the latest consensus step (cmpc_lin_rounds_step_consensus): the last inner round's verdicts on the device,
-    // the node-wide count of every inner round and the loop's outcome on the host
-    int *close = nullptr, *not_close = nullptr;
-    double* delta = nullptr;
-    std::vector<int> trace;
-    bool agreed = false;
 };
 
 namespace {
@@ -227,6 +231,55 @@ int check_step(const RoundsCore* h, int rounds) {
     if (rounds < 0) return fail(h->ctx, CMPC_ERR_ARG, "negative round count");
     if (h->host_exchange() && h->sharded() && rounds > 1)
         return fail(h->ctx, CMPC_ERR_ARG, "host exchange: one round per step (exchange between steps)");
+    return CMPC_OK;
+}
+
+// ---- what the consensus steps of the families share (include/cmpc.h, cmpc_lin_rounds_step_consensus) ----
+
+const cmpc_consensus_opts kConsensusDefaults{3, 2, 12, 0.01, 1e-5};  // NL_EU_N_main.py:102-104
+
+// what both consensus steps check before their loops (`h` is not null)
+int check_consensus(const RoundsCore* h, int steps, const cmpc_consensus_opts& o) {
+    cmpc_ctx* ctx = h->ctx;
+    if (steps < 0) return fail(ctx, CMPC_ERR_ARG, "negative step count");
+    if (o.min_rounds < 1 || o.need < 1 || o.max_rounds < o.min_rounds)
+        return fail(ctx, CMPC_ERR_ARG, "consensus: 1 <= min_rounds <= max_rounds, need >= 1");
+    if (!(o.atol >= 0.0) || !(o.rtol >= 0.0)) return fail(ctx, CMPC_ERR_ARG, "atol and rtol: >= 0 (not NaN)");
+    if (h->host_exchange() && h->sharded())
+        return fail(ctx, CMPC_ERR_ARG, "host exchange: the exchange lies inside a consensus step");
+    return CMPC_OK;
+}
+
+// The stopping rule (cmpc.scenarios.consensus_stop) over the inner rounds of one step: after(count) takes round
+// j's node-wide not-close count and says whether the step stops there.
+struct ConsensusLoop {
+    const cmpc_consensus_opts& co;
+    std::vector<int> trace;
+    bool agreed = false;
+    int streak = 0;
+    bool after(int count) {
+        trace.push_back(count);
+        const int j = (int)trace.size();
+        if (j >= 2) streak = count == 0 ? streak + 1 : 0;  // round 1 compares against the previous step's plan
+        if (streak >= co.need) agreed = true;
+        return j >= co.max_rounds || (agreed && j >= co.min_rounds);
+    }
+};
+
+int consensus_read(RoundsCore* h, const cmpc_consensus_out* o) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
+    if (o->cap < 0) return fail(ctx, CMPC_ERR_ARG, "negative cap");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t B = h->d.batch;
+    if (o->close) HIP_TRY(hipMemcpyAsync(o->close, h->close, 4 * B, hipMemcpyDeviceToHost, s));
+    if (o->delta) HIP_TRY(hipMemcpyAsync(o->delta, h->delta, 8 * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (o->inner_rounds) *o->inner_rounds = (int)h->trace.size();
+    if (o->agreed) *o->agreed = h->agreed ? 1 : 0;
+    if (o->not_close) std::copy_n(h->trace.begin(), std::min((size_t)o->cap, h->trace.size()), o->not_close);
     return CMPC_OK;
 }
 
@@ -559,7 +612,7 @@ int lin_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights
                   {h->C, B * N * mc * nx}, {h->h, B * N * mc}, {h->z, B * nz_mpc(h->md)}, {h->kkt, H * B},
                   {h->nbr, B * nb1}, {h->iters, H * B}, {h->status, H * B}, {h->order, B},
                   {h->A_tab, table ? uA : 0}, {h->B_tab, table ? uB : 0}, {h->close, B}, {h->delta, B},
-                  {h->not_close, 1}});
+                  {h->counts, 2}});
     if (!bytes) {
         delete h;
         return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
@@ -622,7 +675,7 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
                                 {h->traj_all, T * row}, {h->traj_local, B * row}, {h->pose, B * row},
                                 {h->x_agents, B * row * nb1}, {h->z, B * nz_lpv(d.N)}, {h->planes, B * N * 3 * nb1},
                                 {h->kkt, B}, {h->x_dense, B * N * 9}, {h->nbr, B * nb1}, {h->iters, B}, {h->status, B},
-                                {h->infeasible, B}})) {
+                                {h->infeasible, B}, {h->close, B}, {h->delta, B}, {h->counts, 2}})) {
         delete h;
         return fail(ctx, CMPC_ERR_NOMEM, "device allocation of the rounds state failed");
     }
@@ -633,6 +686,8 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
     if (e == hipSuccess) e = in->u_old ? upload(h->u_old, in->u_old, 8 * B * 2, s) : hipMemsetAsync(h->u_old, 0, 8 * B * 2, s);
     if (e == hipSuccess && d.nb) e = upload(h->nbr, in->nbr, 4 * B * d.nb, s);
     if (e == hipSuccess) e = hipMemsetAsync(h->planes, 0, 8 * B * N * 3 * nb1, s);
+    if (e == hipSuccess) e = hipMemsetAsync(h->close, 0, 4 * B, s);  // a read before the first consensus step: zeros
+    if (e == hipSuccess) e = hipMemsetAsync(h->delta, 0, 8 * B, s);
     if (e == hipSuccess && in->traj) e = upload(h->traj_all, in->traj, 8 * T * row, s);
     if (e == hipSuccess && !in->traj)  // the reference's initial `agents` = the predictions' X, Y (misc.py:155-165)
         e = hipMemcpy2DAsync(h->traj_all, 16, h->x_last + 7, 72, 16, B * (N + 1), hipMemcpyDeviceToDevice, s);
@@ -642,6 +697,19 @@ int cmpc_lpv_rounds_create(cmpc_ctx* ctx, const cmpc_lpv_params* prm, const cmpc
         return hip_fail(ctx, e, "cmpc_lpv_rounds_create: upload");
     }
     *out = h;
+    return CMPC_OK;
+}
+
+// Before the first advance of a handle: Last_xPredicted goes from N + 1 rows per agent to N dense ones.  The
+// advance rewrites each agent's dense slot from its solution, but an agent it does not advance (no finite
+// solution) must find its own previous rows there, not bytes of the (N + 1)-row layout: compact the layout first
+// (rows 0..N-1 of each agent).  Nothing once last_rows is N.
+static int compact_x_last(cmpc_lpv_rounds* h, hipStream_t s) {
+    cmpc_ctx* ctx = h->ctx;
+    if (h->last_rows != h->d.N + 1) return CMPC_OK;
+    const size_t w = 8 * (size_t)h->d.N * 9;
+    HIP_TRY(hipMemcpy2DAsync(h->x_dense, w, h->x_last, w + 72, w, h->d.batch, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->x_last, h->x_dense, w * h->d.batch, hipMemcpyDeviceToDevice, s));
     return CMPC_OK;
 }
 
@@ -669,15 +737,7 @@ int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* 
         }
         HIP_TRY(log_mark(h->log, h->rounds_done, 1, s));
         HIP_TRY(hipMemsetAsync(h->infeasible, 0, sizeof(int), s));
-        if (h->last_rows == h->d.N + 1) {
-            // first round: Last_xPredicted goes from N + 1 rows per agent to N dense ones.  The advance
-            // rewrites each agent's dense slot from its solution, but an agent it does not advance
-            // (no finite solution) must find its own previous rows there, not bytes of the
-            // (N + 1)-row layout: compact the layout first (rows 0..N-1 of each agent)
-            const size_t w = 8 * (size_t)h->d.N * 9;
-            HIP_TRY(hipMemcpy2DAsync(h->x_dense, w, h->x_last, w + 72, w, h->d.batch, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(h->x_last, h->x_dense, w * h->d.batch, hipMemcpyDeviceToDevice, s));
-        }
+        if ((rc = compact_x_last(h, s)) != CMPC_OK) return rc;
         if ((rc = cmpc_lpv_advance_dev(ctx, &rd, h->z, h->x0, h->x_last, h->u_last, h->u_old, h->traj_local, h->status,
                                        h->infeasible, s)) != CMPC_OK)
             return rc;
@@ -704,6 +764,94 @@ int cmpc_lpv_rounds_step(cmpc_lpv_rounds* h, int rounds, int* rounds_done, int* 
     if (infeasible) *infeasible = bad;
     return CMPC_OK;
 }
+
+// ---- consensus steps (include/cmpc.h, cmpc_lpv_rounds_step_consensus) ----
+
+// One consensus step: inner rounds of gather, solve, publish and exchange at the handle's state and linearisation
+// (x0, x_last, u_last, u_old, last_rows: untouched by inner rounds) until the stopping rule or the halt rule ends
+// them, then the advance.  *inner: the inner rounds of a step that was counted (0: it was not); *bad: the node-wide
+// infeasible count of the last inner round run.  Returns at the first error; the caller synchronises.
+static int lpv_consensus_step(cmpc_lpv_rounds* h, const cmpc_consensus_opts& co, hipStream_t s, int* inner, int* bad) {
+    cmpc_ctx* ctx = h->ctx;
+    *inner = 0;
+    const bool halt = !(h->d.flags & CMPC_ROUNDS_NO_HALT);
+    const int round = h->rounds_done, nb = h->d.nb;
+    const cmpc_di_dims rd{h->d.batch, h->d.N, nb, h->d.self_offset};
+    const cmpc_lpv_dims ld{h->d.batch, h->d.N, nb, h->last_rows};
+    const cmpc_lpv_data din{h->x0, h->x_last, h->u_last, h->u_old, nb ? h->x_agents : nullptr, h->pose};
+    const cmpc_lpv_out dout{h->z, nb ? h->planes : nullptr, h->kkt, h->iters, h->status};
+    int rc;
+    if ((rc = reselect(h, s)) != CMPC_OK) return rc;
+    HIP_TRY(log_mark(h->log, round, 0, s));
+    ConsensusLoop loop{co};
+    int j = 0;
+    for (;;) {
+        ++j;
+        rc = cmpc_lpv_gather_dev(ctx, &rd, h->nbr, h->traj_all, nb ? h->x_agents : nullptr, h->pose, s);
+        if (rc == CMPC_OK) rc = cmpc_solve_lpv_batch_dev(ctx, &h->prm, &h->track, &ld, &din, &dout, &h->opts, s);
+        if (rc != CMPC_OK) {
+            log_abandon(h->log, round);
+            return rc;
+        }
+        HIP_TRY(hipMemsetAsync(h->counts, 0, 2 * sizeof(int), s));
+        if ((rc = cmpc_lpv_publish_dev(ctx, &rd, h->z, h->traj_all, h->status, co.atol, co.rtol, h->traj_local, h->close,
+                                       h->delta, h->counts, s)) != CMPC_OK)
+            return rc;
+        if ((rc = exchange(h, s)) != CMPC_OK) return rc;
+        // the node's counts, not this rank's: every rank must leave the loop after the same inner round (a rank
+        // that left alone would keep the others waiting in the next all-gather)
+        if (h->sharded() && (rc = cmpc_comm_sum_i32(ctx, h->counts, 2, s)) != CMPC_OK) return rc;
+        int counts[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(counts, h->counts, sizeof counts, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *bad = counts[1];
+        const bool stop = loop.after(counts[0]);
+        if (stop || (halt && counts[1] > 0)) break;  // the reference stops the experiment at an infeasible agent
+    }
+    HIP_TRY(log_mark(h->log, round, 1, s));
+    if ((rc = compact_x_last(h, s)) != CMPC_OK) return rc;
+    // the state and the linearisation point from the final z; traj_local again, with the values the last inner
+    // round exchanged (the publish has counted: no status here)
+    if ((rc = cmpc_lpv_advance_dev(ctx, &rd, h->z, h->x0, h->x_last, h->u_last, h->u_old, h->traj_local, nullptr,
+                                   nullptr, s)) != CMPC_OK)
+        return rc;
+    h->last_rows = h->d.N;
+    if ((rc = log_round(h, round, h->z, h->kkt, h->iters, h->status, s)) != CMPC_OK) return rc;
+    ++h->rounds_done;
+    h->trace = std::move(loop.trace);
+    h->agreed = loop.agreed;
+    *inner = j;
+    return CMPC_OK;
+}
+
+int cmpc_lpv_rounds_step_consensus(cmpc_lpv_rounds* h, int steps, const cmpc_consensus_opts* co, int* steps_done,
+                                   int* inner_total, int* infeasible) {
+    if (!h) return CMPC_ERR_ARG;
+    cmpc_ctx* ctx = h->ctx;
+    const cmpc_consensus_opts o = co ? *co : kConsensusDefaults;
+    int done = 0, total = 0, bad = 0, rc;
+    if ((rc = check_consensus(h, steps, o)) != CMPC_OK) return rc;
+    const bool halt = !(h->d.flags & CMPC_ROUNDS_NO_HALT);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (int i = 0; i < steps && rc == CMPC_OK; ++i) {
+        int inner = 0;
+        rc = lpv_consensus_step(h, o, s, &inner, &bad);
+        if (inner) ++done;
+        total += inner;
+        if (halt && bad) break;  // as cmpc_lpv_rounds_step after a round with an infeasible agent
+    }
+    // one more host synchronisation, also after an error: what was queued has then finished
+    const hipError_t e = hipStreamSynchronize(s);
+    if (steps_done) *steps_done = done;
+    if (inner_total) *inner_total = total;
+    if (infeasible) *infeasible = bad;
+    if (rc != CMPC_OK) return rc;
+    HIP_TRY(e);
+    return CMPC_OK;
+}
+
+int cmpc_lpv_rounds_consensus_read(cmpc_lpv_rounds* h, const cmpc_consensus_out* o) { return consensus_read(h, o); }
 
 int cmpc_lpv_rounds_read(cmpc_lpv_rounds* h, const cmpc_lpv_rounds_out* o) {
     if (!h) return CMPC_ERR_ARG;
@@ -890,9 +1038,8 @@ static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hip
     int rc;
     if ((rc = reselect(h, s)) != CMPC_OK) return rc;
     HIP_TRY(log_mark(h->log, round, 0, s));
-    std::vector<int> trace;
-    bool agreed = false;
-    int streak = 0, j = 0;
+    ConsensusLoop loop{co};
+    int j = 0;
     for (;;) {
         ++j;
         rc = h->T ? cmpc_lin_table_build_dev(ctx, &h->prm, &rd, h->md.nu, &td, &tab, h->t, h->nbr, h->traj_all, h->A,
@@ -906,21 +1053,18 @@ static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hip
         }
         // the next solve's launch order, stream-ordered after this one
         if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) return rc;
-        HIP_TRY(hipMemsetAsync(h->not_close, 0, sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(h->counts, 0, sizeof(int), s));
         if ((rc = cmpc_lin_publish_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->traj_all, co.atol, co.rtol,
-                                       h->traj_local, h->close, h->delta, h->not_close, s)) != CMPC_OK)
+                                       h->traj_local, h->close, h->delta, h->counts, s)) != CMPC_OK)
             return rc;
         if ((rc = exchange(h, s)) != CMPC_OK) return rc;
         // the node's count, not this rank's: every rank must leave the loop after the same inner round (a rank
         // that left alone would keep the others waiting in the next all-gather)
-        if (h->sharded() && (rc = cmpc_comm_sum_i32(ctx, h->not_close, 1, s)) != CMPC_OK) return rc;
+        if (h->sharded() && (rc = cmpc_comm_sum_i32(ctx, h->counts, 1, s)) != CMPC_OK) return rc;
         int count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, h->not_close, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&count, h->counts, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        trace.push_back(count);
-        if (j >= 2) streak = count == 0 ? streak + 1 : 0;  // round 1 compares against the previous step's plan
-        if (streak >= co.need) agreed = true;
-        if (j >= co.max_rounds || (agreed && j >= co.min_rounds)) break;
+        if (loop.after(count)) break;
     }
     HIP_TRY(log_mark(h->log, round, 1, s));
     // x0, u_prev from the final z; traj_local again, with the values the last inner round exchanged
@@ -929,8 +1073,8 @@ static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hip
         return rc;
     ++h->rounds_done;
     if (h->T) h->t = h->mode == CMPC_TABLE_PERIODIC ? (h->t + 1) % h->T : std::min(h->t + 1, h->T - 1);
-    h->trace = std::move(trace);
-    h->agreed = agreed;
+    h->trace = std::move(loop.trace);
+    h->agreed = loop.agreed;
     *inner = j;
     return log_round(h, round, h->z, h->kkt + slot, h->iters + slot, h->status + slot, s);
 }
@@ -939,16 +1083,11 @@ int cmpc_lin_rounds_step_consensus(cmpc_lin_rounds* h, int steps, const cmpc_con
                                    int* inner_total) {
     if (!h) return CMPC_ERR_ARG;
     cmpc_ctx* ctx = h->ctx;
-    const cmpc_consensus_opts o = co ? *co : cmpc_consensus_opts{3, 2, 12, 0.01, 1e-5};  // NL_EU_N_main.py:102-104
-    if (steps < 0) return fail(ctx, CMPC_ERR_ARG, "negative step count");
-    if (o.min_rounds < 1 || o.need < 1 || o.max_rounds < o.min_rounds)
-        return fail(ctx, CMPC_ERR_ARG, "consensus: 1 <= min_rounds <= max_rounds, need >= 1");
-    if (!(o.atol >= 0.0) || !(o.rtol >= 0.0)) return fail(ctx, CMPC_ERR_ARG, "atol and rtol: >= 0 (not NaN)");
-    if (h->host_exchange() && h->sharded())
-        return fail(ctx, CMPC_ERR_ARG, "host exchange: the exchange lies inside a consensus step");
+    const cmpc_consensus_opts o = co ? *co : kConsensusDefaults;
+    int done = 0, total = 0, rc;
+    if ((rc = check_consensus(h, steps, o)) != CMPC_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    int done = 0, total = 0, rc = CMPC_OK;
     for (int i = 0; i < steps && rc == CMPC_OK; ++i) {
         int inner = 0;
         rc = consensus_step(h, o, s, &inner);
@@ -964,22 +1103,7 @@ int cmpc_lin_rounds_step_consensus(cmpc_lin_rounds* h, int steps, const cmpc_con
     return CMPC_OK;
 }
 
-int cmpc_lin_rounds_consensus_read(cmpc_lin_rounds* h, const cmpc_consensus_out* o) {
-    if (!h) return CMPC_ERR_ARG;
-    cmpc_ctx* ctx = h->ctx;
-    if (!o) return fail(ctx, CMPC_ERR_ARG, "null output");
-    if (o->cap < 0) return fail(ctx, CMPC_ERR_ARG, "negative cap");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t B = h->d.batch;
-    if (o->close) HIP_TRY(hipMemcpyAsync(o->close, h->close, 4 * B, hipMemcpyDeviceToHost, s));
-    if (o->delta) HIP_TRY(hipMemcpyAsync(o->delta, h->delta, 8 * B, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (o->inner_rounds) *o->inner_rounds = (int)h->trace.size();
-    if (o->agreed) *o->agreed = h->agreed ? 1 : 0;
-    if (o->not_close) std::copy_n(h->trace.begin(), std::min((size_t)o->cap, h->trace.size()), o->not_close);
-    return CMPC_OK;
-}
+int cmpc_lin_rounds_consensus_read(cmpc_lin_rounds* h, const cmpc_consensus_out* o) { return consensus_read(h, o); }
 
 int cmpc_lin_rounds_get_time(cmpc_lin_rounds* h, int* t) {
     if (!h) return CMPC_ERR_ARG;

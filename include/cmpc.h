@@ -59,7 +59,9 @@ extern "C" {
                                 cmpc_lin_table_build_dev, cmpc_lin_table_round_dev, cmpc_lin_rounds_table_init,
                                 cmpc_lin_rounds_create_table, cmpc_lin_rounds_get_time / _set_time / _table_write;
                                 cmpc_lin_publish_dev, cmpc_consensus_opts, cmpc_consensus_out,
-                                cmpc_lin_rounds_step_consensus, cmpc_lin_rounds_consensus_read */
+                                cmpc_lin_rounds_step_consensus, cmpc_lin_rounds_consensus_read;
+                                cmpc_lpv_publish_dev, cmpc_lpv_rounds_step_consensus,
+                                cmpc_lpv_rounds_consensus_read */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -1180,6 +1182,66 @@ typedef struct {    /* HOST pointers, any may be NULL */
 int cmpc_lin_rounds_step_consensus(cmpc_lin_rounds* h, int steps, const cmpc_consensus_opts* co, int* steps_done,
                                    int* inner_total);
 int cmpc_lin_rounds_consensus_read(cmpc_lin_rounds* h, const cmpc_consensus_out* host_out);
+
+/* ------------------------------------------------------------------------
+ * Consensus steps of the reference's LPV agents (cmpc_lpv_rounds_*): the same step on the handle that drives the
+ * reference's own model.  The model is fixed within a step: every inner round linearises about the previous STEP's
+ * prediction (the handle's x_last, u_last, u_old, last_rows, at its x0), exactly as a plain round does, and only the
+ * coupling is iterated: the collision planes and the coverage weights are re-cut against the positions the round
+ * before published.  Re-linearising about each inner round's own prediction does not settle on this model (a
+ * single agent without neighbours keeps moving by 0.02 to 0.06 per round); DESIGN.md section 4 has the finding.
+ *
+ * cmpc_lpv_publish_dev: one inner round's publication, its convergence test and its feasibility count, in one launch
+ * (one wavefront per agent, no LDS, no scratch, stream-ordered, graph-capturable).  dims = {batch, N, nb (not
+ * read), self_offset} of cmpc_di_dims; z is batch x nz, nz = 12(N+1) + 4N.  For local agent b, with prev =
+ * traj_all[self_offset + b] and new[k] = (z[b, 12k + 7], z[b, 12k + 8]), k = 0..N:
+ *   traj_local[b], close[b], delta[b]: the rule of cmpc_lin_publish_dev above, every expression rounded as written
+ *     (a non-finite value anywhere in z[b]: prev again bit for bit, close 0, delta NaN; otherwise new is copied,
+ *     close = 1 exactly when |prev_e - new_e| <= atol + rtol |new_e| for all 2(N+1) entries, delta = the largest
+ *     |prev_e - new_e|, NaN when any term is) — byte for byte what cmpc_lin_publish_dev gives with ix = 7, iy = 8,
+ *     nx = 9, ns = 3, nu = 2 (the two kernels run one device function);
+ *   counts[0] += the number of agents with close == 0;
+ *   counts[1] += the number of agents whose status is not in {1, 2, -2}: the reference's feasibility rule, the one
+ *     cmpc_lpv_advance_dev applies; skipped (counts[1] untouched) when status is NULL.
+ * Each count is one vector atomic add from one lane of each counted agent: the caller zeroes counts (DEVICE int[2])
+ * on the stream first.  close, delta and counts may each be NULL: that output is skipped, the others are unchanged.
+ * traj_local must not alias traj_all.  cmpc.scenarios.lpv_publish is the numpy statement.
+ * CMPC_ERR_ARG: a NULL dims, z, traj_all or traj_local; N < 1; batch < 0; self_offset < 0; atol or rtol negative or
+ * NaN (+inf is allowed).  batch == 0: CMPC_OK without a launch.
+ *
+ * cmpc_lpv_rounds_step_consensus runs up to `steps` consensus steps; cmpc_consensus_opts, the stopping rule and the
+ * NULL defaults are the linear family's above.  One step, on the context's stream:
+ *   1. CMPC_ROUNDS_RESELECT: cmpc_nbr_select_dev, once; the log's first event;
+ *   2. per inner round: cmpc_lpv_gather_dev; cmpc_solve_lpv_batch_dev on the handle's x0, x_last, u_last, u_old and
+ *      last_rows, all untouched by inner rounds; counts <- 0 (8 bytes); cmpc_lpv_publish_dev; the exchange; sharded
+ *      over the communicator, one cmpc_comm_sum_i32 of both counts; an 8-byte read-back and one stream wait; the
+ *      node-wide not-close count joins the trace and the stopping rule is applied.  Without CMPC_ROUNDS_NO_HALT a
+ *      node-wide infeasible count > 0 ends the inner loop after this round, whatever the stopping rule says;
+ *   3. the log's second event; on the first step x_last goes from N+1 to N dense rows, as in cmpc_lpv_rounds_step;
+ *      cmpc_lpv_advance_dev from the final z with status and infeasible NULL (the publish has counted; it rewrites
+ *      traj_local with the values already exchanged: no second exchange); last_rows = N; the log row; the round
+ *      count moves on once.
+ * After a step the halt rule ended no further step of the call runs (steps_done < steps), as cmpc_lpv_rounds_step
+ * after a round with an infeasible agent.  *infeasible (may be NULL): the node-wide count of the last inner round
+ * run; steps_done / inner_total (may be NULL) as for the linear handle.  A consensus step is ONE round for the log
+ * and the round count; its row holds the last inner round's outputs.  Plain and consensus steps may be mixed on one
+ * handle.  With max_rounds == 1 a step leaves every array a plain cmpc_lpv_rounds_step(h, 1, ..) leaves, byte for
+ * byte, x_last / u_last / u_old included.  A solver error is returned unchanged and the step is not counted: the
+ * log row is abandoned, x0, x_last, u_last, u_old and last_rows are untouched; traj_all may hold the inner rounds
+ * already exchanged.
+ * CMPC_ERR_ARG (nothing is written): a NULL handle; steps < 0; min_rounds < 1, need < 1 or max_rounds <
+ * min_rounds; atol or rtol negative or NaN; a sharded handle with CMPC_ROUNDS_HOST_EXCHANGE.
+ * cmpc_lpv_rounds_consensus_read: as cmpc_lin_rounds_consensus_read.
+ * ---------------------------------------------------------------------- */
+int cmpc_lpv_publish_dev(cmpc_ctx* ctx, const cmpc_di_dims* dims /* batch, N, nb (not read), self_offset */,
+                         const double* z /* batch x nz */, const double* traj_all /* n_total x (N+1) x 2 */,
+                         const int* status /* batch, may be NULL */, double atol, double rtol,
+                         double* traj_local /* batch x (N+1) x 2 */, int* close /* batch, may be NULL */,
+                         double* delta /* batch, may be NULL */, int* counts /* DEVICE int[2], may be NULL */,
+                         void* hip_stream);
+int cmpc_lpv_rounds_step_consensus(cmpc_lpv_rounds* h, int steps, const cmpc_consensus_opts* co, int* steps_done,
+                                   int* inner_total, int* infeasible);
+int cmpc_lpv_rounds_consensus_read(cmpc_lpv_rounds* h, const cmpc_consensus_out* host_out);
 
 
 /* ------------------------------------------------------------------------
