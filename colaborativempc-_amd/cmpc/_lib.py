@@ -199,6 +199,10 @@ class cmpc_lin_params(ct.Structure):   # position = state columns ix, iy
     _fields_ = [("ix", ct.c_int), ("iy", ct.c_int), ("min_dist", ct.c_double), ("wq", ct.c_double)]
 
 
+class cmpc_lin3_params(ct.Structure):  # position = state columns ix, iy, iz (cmpc_lin3_*)
+    _fields_ = [("ix", ct.c_int), ("iy", ct.c_int), ("iz", ct.c_int), ("min_dist", ct.c_double), ("wq", ct.c_double)]
+
+
 class cmpc_lin_dims(ct.Structure):     # mo own rows per stage; mc = mo + nb
     _fields_ = [(k, ct.c_int) for k in ("batch", "N", "nb", "self_offset", "nx", "mo")]
 
@@ -442,6 +446,33 @@ SIGNATURES = {
     "cmpc_lpv_rounds_step_consensus": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(cmpc_consensus_opts), _IP, _IP,
                                                   _IP]),
     "cmpc_lpv_rounds_consensus_read": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_consensus_out)]),
+    "cmpc_lin3_build_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_lin_dims), _IP,
+                                       ct.POINTER(cmpc_lin_own), _DP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_lin3_advance_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_lin_dims), ct.c_int,
+                                         ct.c_int, _DP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_lin3_publish_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_lin_dims), ct.c_int,
+                                         ct.c_int, _DP, _DP, ct.c_double, ct.c_double, _DP, _IP, _DP, _IP, ct.c_void_p]),
+    "cmpc_lin3_round_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_lin_dims), _IP,
+                                       ct.POINTER(cmpc_lin_own), _DP, ct.POINTER(cmpc_mpc_dims),
+                                       ct.POINTER(cmpc_mpc_weights), ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out),
+                                       ct.POINTER(cmpc_opts), _DP, ct.c_void_p]),
+    "cmpc_lin3_table_build_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_lin_dims),
+                                             ct.c_int, ct.POINTER(cmpc_lin_table_dims), ct.POINTER(cmpc_lin_table),
+                                             ct.c_int, _IP, _DP, _DP, _DP, _DP, _DP, _DP, ct.c_void_p]),
+    "cmpc_lin3_table_round_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_lin_dims), _IP,
+                                             ct.POINTER(cmpc_lin_table_dims), ct.POINTER(cmpc_lin_table), ct.c_int, _DP,
+                                             ct.POINTER(cmpc_mpc_dims), ct.POINTER(cmpc_mpc_weights),
+                                             ct.POINTER(cmpc_mpc_data), ct.POINTER(cmpc_mpc_out), ct.POINTER(cmpc_opts),
+                                             _DP, ct.c_void_p]),
+    "cmpc_nbr_select3_dev": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_nbr_dims), _DP, _IP, _DP, ct.c_void_p]),
+    "cmpc_lin_rounds_create3": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_mpc_weights),
+                                           ct.POINTER(cmpc_lin_rounds_dims), ct.POINTER(cmpc_lin_rounds_init),
+                                           ct.POINTER(cmpc_opts), ct.POINTER(ct.c_void_p)]),
+    "cmpc_lin_rounds_create_table3": (ct.c_int, [ct.c_void_p, ct.POINTER(cmpc_lin3_params), ct.POINTER(cmpc_mpc_weights),
+                                                 ct.POINTER(cmpc_lin_rounds_dims),
+                                                 ct.POINTER(cmpc_lin_rounds_table_init), ct.POINTER(cmpc_opts),
+                                                 ct.POINTER(ct.c_void_p)]),
+    "cmpc_lin_rounds_pos_dim": (ct.c_int, [ct.c_void_p, _IP]),
 }
 
 CMPC_COMM_ID_BYTES = 128

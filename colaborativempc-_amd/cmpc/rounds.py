@@ -66,12 +66,13 @@ def select_neighbours_dev(traj_all, nb, batch=None, self_offset=0, window=(0, 0)
     by index, the agent itself left out by index), the result bit-equal to it.  Writes the (batch, nb) int32
     global indices, nearest first, into ``out`` (allocated when None) and returns it; ``dist2`` (batch, nb)
     fp64, optional, receives their scores.  Nearest first is not the reference's index order of ns[i]: it
-    only reorders an agent's collision rows and the columns of ``planes``."""
+    only reorders an agent's collision rows and the columns of ``planes``.  A buffer (n_total, N+1, 3) is scored
+    by the 3-D distance (cmpc_nbr_select3_dev)."""
     import torch
 
-    if traj_all.dim() != 3 or traj_all.shape[2] != 2 or traj_all.dtype != torch.float64 or not traj_all.is_cuda or \
-            not traj_all.is_contiguous():
-        raise ValueError("traj_all: a contiguous (n_total, N+1, 2) float64 CUDA tensor")
+    if traj_all.dim() != 3 or traj_all.shape[2] not in (2, 3) or traj_all.dtype != torch.float64 or \
+            not traj_all.is_cuda or not traj_all.is_contiguous():
+        raise ValueError("traj_all: a contiguous (n_total, N+1, 2) or (n_total, N+1, 3) float64 CUDA tensor")
     n_total, N = int(traj_all.shape[0]), int(traj_all.shape[1]) - 1
     batch = n_total - self_offset if batch is None else int(batch)
     if out is None:
@@ -84,9 +85,9 @@ def select_neighbours_dev(traj_all, nb, batch=None, self_offset=0, window=(0, 0)
     if stream is None:
         stream = torch.cuda.current_stream(traj_all.device)
     dims = L.cmpc_nbr_dims(batch, N, int(nb), int(self_offset), n_total, int(window[0]), int(window[1]))
-    ctx.check(ctx.lib.cmpc_nbr_select_dev(ctx.h, ct.byref(dims), _tptr(traj_all), _tptr(out),
-                                          None if dist2 is None else _tptr(dist2),
-                                          ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+    select = ctx.lib.cmpc_nbr_select3_dev if traj_all.shape[2] == 3 else ctx.lib.cmpc_nbr_select_dev
+    ctx.check(select(ctx.h, ct.byref(dims), _tptr(traj_all), _tptr(out), None if dist2 is None else _tptr(dist2),
+                     ct.c_void_p(getattr(stream, "cuda_stream", stream))))
     return out
 
 
@@ -161,11 +162,25 @@ def log_round_dev(z, nx, nu, ns, N, look_col, row=None, kkt=None, iters=None, st
 
 
 def _lin_params(prm):
-    """cmpc_lin_params of a ``prm`` dict(ix, iy, min_dist, wq)."""
+    """cmpc_lin_params of a ``prm`` dict(ix, iy, min_dist, wq); cmpc_lin3_params when it has ``iz``."""
+    if "iz" in prm:
+        return L.cmpc_lin3_params(int(prm["ix"]), int(prm["iy"]), int(prm["iz"]), float(prm["min_dist"]),
+                                  float(prm["wq"]))
     return L.cmpc_lin_params(int(prm["ix"]), int(prm["iy"]), float(prm["min_dist"]), float(prm["wq"]))
 
 
-def _lin_args(traj_all, nbr, own, self_offset, ctx, stream):
+def _pos_dim(prm):
+    """Coordinates of a position under ``prm``: 3 with ``iz`` (the cmpc_lin3_* entries, buffers x 3), else 2."""
+    return 3 if "iz" in prm else 2
+
+
+def _lin_fn(ctx, prm, name):
+    """The family's device entry ``name`` ("build_dev", ..) for ``prm``: cmpc_lin3_<name> with ``iz``, else
+    cmpc_lin_<name>."""
+    return getattr(ctx.lib, ("cmpc_lin3_" if "iz" in prm else "cmpc_lin_") + name)
+
+
+def _lin_args(traj_all, nbr, own, self_offset, ctx, stream, pd=2):
     """What the three linear-model wrappers share: the shapes read off the tensors, cmpc_lin_dims, cmpc_lin_own."""
     import torch
 
@@ -174,8 +189,8 @@ def _lin_args(traj_all, nbr, own, self_offset, ctx, stream):
     C_own, h_own = own.get("C_own"), own.get("h_own")
     mo = 0 if C_own is None else int(C_own.shape[2])
     nb = 0 if nbr is None else int(nbr.shape[1])
-    if traj_all.dim() != 3 or tuple(traj_all.shape[1:]) != (N + 1, 2) or (mo and tuple(h_own.shape) != (B, N, mo)):
-        raise ValueError("traj_all (n_total, N+1, 2), qlin_own (B, N+1, nx), C_own (B, N, mo, nx), h_own (B, N, mo)")
+    if traj_all.dim() != 3 or tuple(traj_all.shape[1:]) != (N + 1, pd) or (mo and tuple(h_own.shape) != (B, N, mo)):
+        raise ValueError(f"traj_all (n_total, N+1, {pd}), qlin_own (B, N+1, nx), C_own (B, N, mo, nx), h_own (B, N, mo)")
     ctx = ctx or L.default_context(traj_all.device.index)
     if stream is None:
         stream = torch.cuda.current_stream(traj_all.device)
@@ -192,7 +207,7 @@ def lin_build_dev(prm, own, nbr, traj_all, self_offset=0, out=None, ctx=None, st
     ``traj_all`` (n_total, N+1, 2).  Writes ``out`` = (qlin, C, h) (allocated when None) and returns it."""
     import torch
 
-    ctx, dims, lo, pn, st = _lin_args(traj_all, nbr, own, self_offset, ctx, stream)
+    ctx, dims, lo, pn, st = _lin_args(traj_all, nbr, own, self_offset, ctx, stream, _pos_dim(prm))
     B, N, nx, mc = dims.batch, dims.N, dims.nx, dims.mo + dims.nb
     if out is None:
         out = tuple(torch.empty(shp, dtype=torch.float64, device=traj_all.device)
@@ -203,8 +218,8 @@ def lin_build_dev(prm, own, nbr, traj_all, self_offset=0, out=None, ctx=None, st
     if B == 0 or mc == 0:   # empty tensors have no address to hand over; nothing to build beyond the copy of qlin
         qlin.copy_(own["qlin_own"])
         return out
-    ctx.check(ctx.lib.cmpc_lin_build_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(lo),
-                                         _tptr(traj_all), _tptr(qlin), _tptr(C), _tptr(h), st))
+    ctx.check(_lin_fn(ctx, prm, "build_dev")(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(lo),
+                                             _tptr(traj_all), _tptr(qlin), _tptr(C), _tptr(h), st))
     return out
 
 
@@ -216,17 +231,17 @@ def lin_advance_dev(prm, z, nx, nu, ns, N, x0, u_prev, traj_local, ctx=None, str
 
     B = int(z.shape[0])
     if z.dim() != 2 or z.shape[1] != (nx + ns) * (N + 1) + 2 * nu * N or tuple(x0.shape) != (B, nx) or \
-            tuple(u_prev.shape) != (B, nu) or tuple(traj_local.shape) != (B, N + 1, 2):
-        raise ValueError("z (B, (nx+ns)(N+1) + 2 nu N), x0 (B, nx), u_prev (B, nu), traj_local (B, N+1, 2)")
+            tuple(u_prev.shape) != (B, nu) or tuple(traj_local.shape) != (B, N + 1, _pos_dim(prm)):
+        raise ValueError(f"z (B, (nx+ns)(N+1) + 2 nu N), x0 (B, nx), u_prev (B, nu), traj_local (B, N+1, {_pos_dim(prm)})")
     if B == 0:
         return
     ctx = ctx or L.default_context(z.device.index)
     if stream is None:
         stream = torch.cuda.current_stream(z.device)
     dims = L.cmpc_lin_dims(B, int(N), 0, 0, int(nx), 0)
-    ctx.check(ctx.lib.cmpc_lin_advance_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), int(ns), int(nu),
-                                           _tptr(z), _tptr(x0), _tptr(u_prev), _tptr(traj_local),
-                                           ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+    ctx.check(_lin_fn(ctx, prm, "advance_dev")(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), int(ns), int(nu),
+                                               _tptr(z), _tptr(x0), _tptr(u_prev), _tptr(traj_local),
+                                               ct.c_void_p(getattr(stream, "cuda_stream", stream))))
 
 
 def lin_publish_dev(prm, z, nx, nu, ns, N, traj_all, traj_local, atol=0.01, rtol=1e-5, self_offset=0, close=None,
@@ -240,12 +255,12 @@ def lin_publish_dev(prm, z, nx, nu, ns, N, traj_all, traj_local, atol=0.01, rtol
     must not alias ``traj_all``."""
     import torch
 
-    B = int(z.shape[0])
+    B, pd = int(z.shape[0]), _pos_dim(prm)
     if z.dim() != 2 or z.shape[1] != (nx + ns) * (N + 1) + 2 * nu * N or traj_all.dim() != 3 or \
-            tuple(traj_all.shape[1:]) != (N + 1, 2) or tuple(traj_local.shape) != (B, N + 1, 2) or \
+            tuple(traj_all.shape[1:]) != (N + 1, pd) or tuple(traj_local.shape) != (B, N + 1, pd) or \
             self_offset < 0 or self_offset + B > traj_all.shape[0]:
-        raise ValueError("z (B, (nx+ns)(N+1) + 2 nu N), traj_all (n_total >= self_offset + B, N+1, 2), traj_local "
-                         "(B, N+1, 2)")
+        raise ValueError(f"z (B, (nx+ns)(N+1) + 2 nu N), traj_all (n_total >= self_offset + B, N+1, {pd}), traj_local "
+                         f"(B, N+1, {pd})")
     for name, t, dt, shp in (("close", close, torch.int32, (B,)), ("delta", delta, torch.float64, (B,)),
                              ("not_close", not_close, torch.int32, (1,))):
         if t is not None and (t.device != z.device or t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous()):
@@ -256,10 +271,10 @@ def lin_publish_dev(prm, z, nx, nu, ns, N, traj_all, traj_local, atol=0.01, rtol
     if stream is None:
         stream = torch.cuda.current_stream(z.device)
     dims = L.cmpc_lin_dims(B, int(N), 0, int(self_offset), int(nx), 0)
-    ctx.check(ctx.lib.cmpc_lin_publish_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), int(ns), int(nu), _tptr(z),
-                                           _tptr(traj_all), float(atol), float(rtol), _tptr(traj_local), _tptr(close),
-                                           _tptr(delta), _tptr(not_close),
-                                           ct.c_void_p(getattr(stream, "cuda_stream", stream))))
+    ctx.check(_lin_fn(ctx, prm, "publish_dev")(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), int(ns), int(nu),
+                                               _tptr(z), _tptr(traj_all), float(atol), float(rtol), _tptr(traj_local),
+                                               _tptr(close), _tptr(delta), _tptr(not_close),
+                                               ct.c_void_p(getattr(stream, "cuda_stream", stream))))
 
 
 def lpv_publish_dev(z, N, traj_all, traj_local, status=None, atol=0.01, rtol=1e-5, self_offset=0, close=None, delta=None,
@@ -302,18 +317,18 @@ def lin_round_dev(prm, own, nbr, traj_all, shared, dev, out, traj_local, self_of
     exchange traj_local -> traj_all stays the caller's."""
     from .solver import PER_AGENT
 
-    ctx, dims, lo, pn, st = _lin_args(traj_all, nbr, own, self_offset, ctx, stream)
+    ctx, dims, lo, pn, st = _lin_args(traj_all, nbr, own, self_offset, ctx, stream, _pos_dim(prm))
     w, keep = _weights(shared)
     data = L.cmpc_mpc_data(*[_tptr(dev[k]) for k in PER_AGENT])
     o_ = L.cmpc_mpc_out(_tptr(out["z"]), _tptr(out.get("kkt")), _tptr(out.get("iters")), _tptr(out.get("status")))
-    ctx.check(ctx.lib.cmpc_lin_round_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(lo),
-                                         _tptr(traj_all), ct.byref(_dims(shared, dims.batch)), ct.byref(w),
-                                         ct.byref(data), ct.byref(o_), None if opts is None else ct.byref(opts),
-                                         _tptr(traj_local), st))
+    ctx.check(_lin_fn(ctx, prm, "round_dev")(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(lo),
+                                             _tptr(traj_all), ct.byref(_dims(shared, dims.batch)), ct.byref(w),
+                                             ct.byref(data), ct.byref(o_), None if opts is None else ct.byref(opts),
+                                             _tptr(traj_local), st))
     del keep
 
 
-def _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream):
+def _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream, pd=2):
     """What the two stage-table wrappers share: the shapes read off the table's tensors (A (B, T, nx, nx), B (B, T,
     nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo); C / h None when mo = 0), cmpc_lin_dims,
     cmpc_lin_table_dims, cmpc_lin_table."""
@@ -325,10 +340,10 @@ def _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream):
     mo = 0 if C is None else int(C.shape[2])
     nb = 0 if nbr is None else int(nbr.shape[1])
     if tuple(A.shape) != (B, T, nx, nx) or tuple(Bm.shape) != (B, T, nx, nu) or traj_all.dim() != 3 or \
-            tuple(traj_all.shape[1:]) != (N + 1, 2) or (mo and (tuple(C.shape) != (B, T, mo, nx) or
+            tuple(traj_all.shape[1:]) != (N + 1, pd) or (mo and (tuple(C.shape) != (B, T, mo, nx) or
                                                                  tuple(h.shape) != (B, T, mo))):
         raise ValueError("table: A (B, T, nx, nx), B (B, T, nx, nu), qlin (B, T, nx), C (B, T, mo, nx), h (B, T, mo); "
-                         "traj_all (n_total, N+1, 2)")
+                         f"traj_all (n_total, N+1, {pd})")
     ctx = ctx or L.default_context(traj_all.device.index)
     if stream is None:
         stream = torch.cuda.current_stream(traj_all.device)
@@ -348,7 +363,8 @@ def lin_table_build_dev(prm, table, t, N, nbr, traj_all, mode=L.CMPC_TABLE_HOLD,
     Writes ``out`` = (A, B, qlin, C, h) (allocated when None) and returns it."""
     import torch
 
-    ctx, dims, nu, td, tab, pn, st = _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream)
+    ctx, dims, nu, td, tab, pn, st = _lin_table_args(table, N, nbr, traj_all, mode, self_offset, ctx, stream,
+                                                     _pos_dim(prm))
     B, N, nx, mc = dims.batch, dims.N, dims.nx, dims.mo + dims.nb
     shapes = ((B, N, nx, nx), (B, N, nx, nu), (B, N + 1, nx), (B, N, mc, nx), (B, N, mc))
     if out is None:
@@ -359,9 +375,9 @@ def lin_table_build_dev(prm, table, t, N, nbr, traj_all, mode=L.CMPC_TABLE_HOLD,
         return out
     # (no rows at all: C and h are empty and never written; the entry point still wants an address)
     spare = torch.empty(1, dtype=torch.float64, device=traj_all.device) if mc == 0 else None
-    ctx.check(ctx.lib.cmpc_lin_table_build_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), nu, ct.byref(td),
-                                               ct.byref(tab), int(t), pn, _tptr(traj_all),
-                                               *[_tptr(o if o.numel() else spare) for o in out], st))
+    ctx.check(_lin_fn(ctx, prm, "table_build_dev")(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), nu, ct.byref(td),
+                                                   ct.byref(tab), int(t), pn, _tptr(traj_all),
+                                                   *[_tptr(o if o.numel() else spare) for o in out], st))
     return out
 
 
@@ -374,15 +390,15 @@ def lin_table_round_dev(prm, table, t, nbr, traj_all, shared, dev, out, traj_loc
     from .solver import PER_AGENT
 
     ctx, dims, nu, td, tab, pn, st = _lin_table_args(table, int(shared["N"]), nbr, traj_all, mode, self_offset, ctx,
-                                                     stream)
+                                                     stream, _pos_dim(prm))
     w, keep = _weights(shared)
     data = L.cmpc_mpc_data(*[_tptr(dev[k]) for k in PER_AGENT])
     o_ = L.cmpc_mpc_out(_tptr(out["z"]), _tptr(out.get("kkt")), _tptr(out.get("iters")), _tptr(out.get("status")))
-    ctx.check(ctx.lib.cmpc_lin_table_round_dev(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(td),
-                                               ct.byref(tab), int(t), _tptr(traj_all),
-                                               ct.byref(_dims(shared, dims.batch)), ct.byref(w), ct.byref(data),
-                                               ct.byref(o_), None if opts is None else ct.byref(opts),
-                                               _tptr(traj_local), st))
+    ctx.check(_lin_fn(ctx, prm, "table_round_dev")(ctx.h, ct.byref(_lin_params(prm)), ct.byref(dims), pn, ct.byref(td),
+                                                   ct.byref(tab), int(t), _tptr(traj_all),
+                                                   ct.byref(_dims(shared, dims.batch)), ct.byref(w), ct.byref(data),
+                                                   ct.byref(o_), None if opts is None else ct.byref(opts),
+                                                   _tptr(traj_local), st))
     del keep
 
 
@@ -467,15 +483,17 @@ class _RoundsHandle:
         if log or log_separation:
             self._call("log_enable", int(log), L.CMPC_LOG_SEPARATION if log_separation else 0)
 
+    pd = 2   # coordinates of a position: 3 on a linear-model handle whose ``prm`` has ``iz``
+
     def get_traj(self):
-        t = np.zeros((self.B, self.N + 1, 2))
+        t = np.zeros((self.B, self.N + 1, self.pd))
         self._call("get_traj", L.dptr(t))
         return t
 
     def set_traj(self, traj_all):
         t = L.f64(traj_all)
-        if t.shape != (self.n, self.N + 1, 2):
-            raise ValueError("traj_all: (n_total, N+1, 2)")
+        if t.shape != (self.n, self.N + 1, self.pd):
+            raise ValueError(f"traj_all: (n_total, N+1, {self.pd})")
         self._call("set_traj", L.dptr(t))
 
     def close(self):
@@ -1019,17 +1037,22 @@ class LinRoundsHandle(_RoundsHandle):
     Qs, u_ub, u_lb, row_slack, row_sign); ``prm``: dict(ix, iy, min_dist, wq); ``own``: dict(qlin_own, C_own,
     h_own) (``scenarios.lin_rows``); population arrays A (n, N, nx, nx), B (n, N, nx, nu), x0 (n, nx), u_prev
     (n, nu), nbr (n, nb), own arrays with leading dimension n, traj (n, N+1, 2): this handle takes the contiguous
-    shard ``rank`` of ``world``.  ``opts``: a ``_lib.opts`` for the solver (None: defaults).  ``host_exchange``,
-    ``reselect``, ``lpt``, ``history``, ``log``, ``log_separation``: as ``DIRoundsHandle`` (``lpt`` None: its
-    default rule).  ``set_state`` replaces the predicted state by a measured one."""
+    shard ``rank`` of ``world``.  A ``prm`` with ``iz`` makes the positions 3-D (cmpc_lin_rounds_create3): traj and
+    ``get_traj`` / ``set_traj`` are x 3, and re-selection and the log's separation use the 3-D distance.
+    ``opts``: a ``_lib.opts`` for the solver (None: defaults).  ``host_exchange``, ``reselect``, ``lpt``,
+    ``history``, ``log``, ``log_separation``: as ``DIRoundsHandle`` (``lpt`` None: its default rule).
+    ``set_state`` replaces the predicted state by a measured one."""
 
     _fn = "cmpc_lin_rounds_"
 
-    def _shard(self, shared, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history):
+    def _shard(self, shared, prm, traj, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history):
         """The wrapper's attributes and cmpc_lin_rounds_dims; returns (this rank's slice, nbr as (n, nb) int32)."""
         n = int(np.shape(x0)[0])
         if n % world:
             raise ValueError("agents must be divisible by the number of ranks")
+        self.pd = _pos_dim(prm)
+        if np.shape(traj) != (n, int(shared["N"]) + 1, self.pd):
+            raise ValueError(f"traj: (n, N+1, {self.pd})")
         self.ctx = ctx or L.default_context(0)
         self.B, self.n, self.N = n // world, n, int(shared["N"])
         sl = slice(rank * self.B, (rank + 1) * self.B)
@@ -1046,7 +1069,8 @@ class LinRoundsHandle(_RoundsHandle):
 
     def __init__(self, shared, prm, own, A, B, x0, u_prev, nbr, traj, rank=0, world=1, ctx=None, opts=None,
                  host_exchange=False, reselect=False, lpt=None, history=1, log=0, log_separation=False):
-        sl, nbr = self._shard(shared, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history)
+        sl, nbr = self._shard(shared, prm, traj, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt,
+                              history)
         w, wkeep = _weights(shared)
         opt = lambda a: None if a is None or self.mo == 0 else L.f64(np.asarray(a)[sl])   # noqa: E731
         keep = [L.f64(np.asarray(A)[sl]), L.f64(np.asarray(B)[sl]), L.f64(np.asarray(x0)[sl]),
@@ -1055,7 +1079,7 @@ class LinRoundsHandle(_RoundsHandle):
         init = L.cmpc_lin_rounds_init(*[L.dptr(a) for a in keep[:7]], L.iptr(keep[7]) if self.nb else None,
                                       L.dptr(keep[8]))
         self._create((_lin_params(prm), w, self.dims, init, opts if opts is not None else L.opts()), log,
-                     log_separation)
+                     log_separation, create="create3" if self.pd == 3 else "create")
 
     @classmethod
     def of_di(cls, scen, tol=None, max_iter=None, fp32=False, **kw):
@@ -1066,6 +1090,24 @@ class LinRoundsHandle(_RoundsHandle):
         lin = lin_of_di(scen)
         return cls(scen.shared, lin["prm"], lin["own"], scen.A, scen.B, scen.x0, scen.u_prev, scen.nbr, scen.traj,
                    opts=_di_opts(tol, max_iter, fp32), **kw)
+
+    @classmethod
+    def of_di3(cls, scen, alt, tol=None, max_iter=None, fp32=False, **kw):
+        """The handle of a 3-D ``scenarios.DIScenario`` with 3-D positions (``scenarios.lin3_of_di``): the agents at
+        altitude ``alt`` (a scalar or (n,)), the altitude in the collision planes, the coverage term and the
+        neighbour selection.  With ``alt`` one value the first round is ``of_di``'s."""
+        from .scenarios import lin3_of_di
+
+        lin = lin3_of_di(scen, alt)
+        return cls(scen.shared, lin["prm"], lin["own"], scen.A, scen.B, lin["x0"], scen.u_prev, scen.nbr, lin["traj"],
+                   opts=_di_opts(tol, max_iter, fp32), **kw)
+
+    @property
+    def pos_dim(self):
+        """Coordinates of a position on this handle (cmpc_lin_rounds_pos_dim): 2, or 3 when ``prm`` has ``iz``."""
+        pd = ct.c_int()
+        self._call("pos_dim", ct.byref(pd))
+        return pd.value
 
     def step(self, rounds=1):
         """Runs ``rounds`` rounds (one host synchronisation, at the end); returns the number done."""
@@ -1127,7 +1169,8 @@ class LinTableRoundsHandle(LinRoundsHandle):
         from .scenarios import lin_table_rows_of
 
         self.T, self.mode = lin_table_rows_of(table), int(mode)
-        sl, nbr = self._shard(shared, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt, history)
+        sl, nbr = self._shard(shared, prm, traj, x0, nbr, rank, world, ctx, opts, host_exchange, reselect, lpt,
+                              history)
         w, wkeep = _weights(shared)
         opt = lambda a: None if a is None or self.mo == 0 else L.f64(np.asarray(a)[sl])   # noqa: E731
         keep = [L.f64(np.asarray(table[k])[sl]) for k in ("A", "B", "qlin")] + \
@@ -1136,7 +1179,7 @@ class LinTableRoundsHandle(LinRoundsHandle):
         init = L.cmpc_lin_rounds_table_init(self.T, self.mode, int(t0), *[L.dptr(a) for a in keep],
                                             L.iptr(knbr) if self.nb else None, L.dptr(ktraj))
         self._create((_lin_params(prm), w, self.dims, init, opts if opts is not None else L.opts()), log,
-                     log_separation, create="create_table")
+                     log_separation, create="create_table3" if self.pd == 3 else "create_table")
 
     @classmethod
     def of_di(cls, scen, tol=None, max_iter=None, fp32=False, T=1, **kw):
@@ -1146,6 +1189,15 @@ class LinTableRoundsHandle(LinRoundsHandle):
 
         lin = lin_table_of_di(scen, T)
         return cls(scen.shared, lin["prm"], lin["table"], scen.x0, scen.u_prev, scen.nbr, scen.traj, mode=lin["mode"],
+                   opts=_di_opts(tol, max_iter, fp32), **kw)
+
+    @classmethod
+    def of_di3(cls, scen, alt, tol=None, max_iter=None, fp32=False, T=1, **kw):
+        """``LinRoundsHandle.of_di3`` as a stage table of ``T`` equal rows under CMPC_TABLE_HOLD."""
+        from .scenarios import lin3_of_di, lin_table_of_di
+
+        lin, tab = lin3_of_di(scen, alt), lin_table_of_di(scen, T)
+        return cls(scen.shared, lin["prm"], tab["table"], lin["x0"], scen.u_prev, scen.nbr, lin["traj"], mode=tab["mode"],
                    opts=_di_opts(tol, max_iter, fp32), **kw)
 
     @property

@@ -104,7 +104,8 @@ def select_neighbours(traj, nb, window=(0, 0), rows=None, return_dist2=False):
     int32 global indices, nearest first (and their scores with ``return_dist2``).  Window (0, 0) is
     "nearest now" — on distinct distances what ``nearest_neighbours`` gives for the stage-0 positions;
     (0, N) is the closest predicted approach.  The reference's ns[i] (LPV_HP_N_main.py:82-85) is in
-    index order: nearest first only reorders an agent's collision rows and the columns of ``planes``."""
+    index order: nearest first only reorders an agent's collision rows and the columns of ``planes``.
+    A buffer (n, N+1, 3) is scored by dx*dx + dy*dy + dz*dz, summed left to right (cmpc_nbr_select3_dev)."""
     traj = np.asarray(traj, np.float64)
     n, (k0, k1) = traj.shape[0], window
     if not (0 <= k0 <= k1 < traj.shape[1]) or not (0 <= nb < n):
@@ -118,7 +119,11 @@ def select_neighbours(traj, nb, window=(0, 0), rows=None, return_dist2=False):
             r = rows[i:i + step]
             dx = w[None, :, :, 0] - w[r, None, :, 0]
             dy = w[None, :, :, 1] - w[r, None, :, 1]
-            score[i:i + step] = (dx * dx + dy * dy).min(axis=2)
+            d2 = dx * dx + dy * dy
+            if traj.shape[2] == 3:
+                dz = w[None, :, :, 2] - w[r, None, :, 2]
+                d2 = d2 + dz * dz
+            score[i:i + step] = d2.min(axis=2)
     score[np.isnan(score)] = np.inf
     j = np.broadcast_to(np.arange(n), score.shape)
     order = np.lexsort((j, score), axis=1)                 # by score, then by index
@@ -157,7 +162,11 @@ def lin_rows(prm, own, nbr, traj, self_offset=0):
     ``own``: dict(qlin_own (B, N+1, nx), C_own (B, N, mo, nx), h_own (B, N, mo)), C_own / h_own may be None when
     the agents have no own rows; ``nbr`` (B, nb) global indices into ``traj`` (n_total, N+1, 2); the local agents
     are rows self_offset .. self_offset + B of ``traj``.  Returns (qlin (B, N+1, nx), C (B, N, mo+nb, nx),
-    h (B, N, mo+nb)).  A neighbour on the agent's own point gives NaN rows and cost at that stage."""
+    h (B, N, mo+nb)).  A neighbour on the agent's own point gives NaN rows and cost at that stage.
+    A ``prm`` with the key ``iz`` selects the 3-D rule (cmpc_lin3_build_dev): ``traj`` is (n_total, N+1, 3), the
+    third coordinate joins every sum (left to right) and column iz gets the normal's third component."""
+    if "iz" in prm:
+        return _lin3_rows(prm, own, nbr, traj, self_offset)
     ix, iy, d, wq = int(prm["ix"]), int(prm["iy"]), float(prm["min_dist"]), float(prm["wq"])
     q_own = np.asarray(own["qlin_own"], np.float64)
     B, N, nx = q_own.shape[0], q_own.shape[1] - 1, q_own.shape[2]
@@ -197,21 +206,88 @@ def lin_rows(prm, own, nbr, traj, self_offset=0):
     return qlin, C, h
 
 
+def _pos3(prm, nx):
+    """The three position columns of a 3-D ``prm``, checked: pairwise different, each in [0, nx)."""
+    cols = tuple(int(prm[k]) for k in ("ix", "iy", "iz"))
+    if len(set(cols)) != 3 or not all(0 <= c < nx for c in cols):
+        raise ValueError("position columns ix, iy, iz: pairwise different, each in [0, nx)")
+    return cols
+
+
+def _lin3_rows(prm, own, nbr, traj, self_offset=0):
+    """``lin_rows`` for a ``prm`` with ``iz`` (cmpc_lin3_build_dev, include/cmpc.h): the same statement with three
+    coordinates, every sum left to right."""
+    d, wq = float(prm["min_dist"]), float(prm["wq"])
+    q_own = np.asarray(own["qlin_own"], np.float64)
+    B, N, nx = q_own.shape[0], q_own.shape[1] - 1, q_own.shape[2]
+    C_own = np.zeros((B, N, 0, nx)) if own.get("C_own") is None else np.asarray(own["C_own"], np.float64)
+    h_own = np.zeros((B, N, 0)) if own.get("h_own") is None else np.asarray(own["h_own"], np.float64)
+    mo = C_own.shape[2]
+    nbr = np.asarray(nbr, np.int64).reshape(B, -1)
+    nb = nbr.shape[1]
+    traj = np.asarray(traj, np.float64)
+    ix, iy, iz = _pos3(prm, nx)
+    if C_own.shape != (B, N, mo, nx) or h_own.shape != (B, N, mo) or traj.ndim != 3 or traj.shape[1:] != (N + 1, 3):
+        raise ValueError("lin_rows (3-D): C_own (B, N, mo, nx), h_own (B, N, mo), traj (n, N+1, 3)")
+    C = np.zeros((B, N, mo + nb, nx))
+    h = np.zeros((B, N, mo + nb))
+    C[:, :, :mo] = C_own
+    h[:, :, :mo] = h_own
+    me = traj[self_offset:self_offset + B]
+    px, py, pz = np.zeros((B, N)), np.zeros((B, N)), np.zeros((B, N))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i in range(nb):
+            nt = traj[nbr[:, i]]
+            ex, ey, ez = (me[:, :-1, c] for c in range(3))                                  # planes: row k-1
+            nx_, ny_, nz_ = (nt[:, :-1, c] for c in range(3))
+            dx, dy, dz = nx_ - ex, ny_ - ey, nz_ - ez
+            nrm = np.sqrt(dx * dx + dy * dy + dz * dz)
+            ax, ay, az = dx / nrm, dy / nrm, dz / nrm
+            bb = -0.5 * (ax * (ex + nx_) + ay * (ey + ny_) + az * (ez + nz_))
+            qx, qy, qz = (me[:, 1:, c] - nt[:, 1:, c] for c in range(3))                    # weights: row k
+            wgt = (2.0 * d - np.sqrt(qx * qx + qy * qy + qz * qz)) / nb
+            C[:, :, mo + i, ix] = ax
+            C[:, :, mo + i, iy] = ay
+            C[:, :, mo + i, iz] = az
+            h[:, :, mo + i] = -d / 2 - bb
+            px = px + wq * wgt * ax
+            py = py + wq * wgt * ay
+            pz = pz + wq * wgt * az
+        qlin = q_own.copy()
+        qlin[:, 1:, ix] = q_own[:, 1:, ix] + px
+        qlin[:, 1:, iy] = q_own[:, 1:, iy] + py
+        qlin[:, 1:, iz] = q_own[:, 1:, iz] + pz
+    return qlin, C, h
+
+
+def _positions(prm, xi):
+    """The predicted positions (B, N+1, 2 | 3) out of the stage states ``xi`` (B, N+1, nxe): columns ix, iy, and
+    iz when ``prm`` has it."""
+    cols = [int(prm["ix"]), int(prm["iy"])] + ([int(prm["iz"])] if "iz" in prm else [])
+    return np.stack([xi[:, :, c] for c in cols], axis=-1)
+
+
 def lin_advance(prm, z, nx, nu, ns, N, x0, u_prev, traj_local):
     """Host statement of the family's advance (cmpc_lin_advance_dev): from ``z`` (B, nz) in the reference layout,
     nxe = nx + ns: x0 <- z[nxe : nxe+nx], u_prev <- z[nxe(N+1) : +nu], traj_local[k] <- (z[k nxe + ix],
     z[k nxe + iy]).  An agent whose z holds any non-finite value keeps all three.  Returns new (x0, u_prev,
-    traj_local); the arguments are left alone."""
+    traj_local); the arguments are left alone.  With ``iz`` in ``prm`` (cmpc_lin3_advance_dev) traj_local is
+    (B, N+1, 3) and traj_local[k] <- (z[k nxe + ix], z[k nxe + iy], z[k nxe + iz])."""
     z = np.asarray(z, np.float64)
     ix, iy, nxe = int(prm["ix"]), int(prm["iy"]), nx + ns
     if z.ndim != 2 or z.shape[1] != nxe * (N + 1) + 2 * nu * N:
         raise ValueError("z: (batch, (nx+ns)(N+1) + 2 nu N)")
     x0, u_prev, traj_local = (np.array(a, np.float64) for a in (x0, u_prev, traj_local))
+    if "iz" in prm and (_pos3(prm, nx) and traj_local.shape != (z.shape[0], N + 1, 3)):
+        raise ValueError("lin_advance (3-D): traj_local (B, N+1, 3)")
     ok = np.isfinite(z).all(axis=1)
     xi = z[:, :nxe * (N + 1)].reshape(-1, N + 1, nxe)
     x0[ok] = xi[ok, 1, :nx]
     u_prev[ok] = z[ok, nxe * (N + 1):nxe * (N + 1) + nu]
-    traj_local[ok] = np.stack([xi[ok, :, ix], xi[ok, :, iy]], axis=-1)
+    if "iz" in prm:
+        traj_local[ok] = _positions(prm, xi[ok])
+    else:
+        traj_local[ok] = np.stack([xi[ok, :, ix], xi[ok, :, iy]], axis=-1)
     return x0, u_prev, traj_local
 
 
@@ -222,19 +298,23 @@ def lin_publish(prm, z, nx, nu, ns, N, traj_all, atol=0.01, rtol=1e-5, self_offs
     whose z holds any non-finite value publishes ``prev`` again, with close = 0 and delta = NaN; every other agent
     publishes ``new``, close = all(|prev - new| <= atol + rtol |new|) (numpy's allclose: a NaN is never close) and
     delta = max |prev - new| (numpy's max: NaN when any term is).  Returns (traj_local (B, N+1, 2), close (B,) int32,
-    delta (B,), not_close = the number of agents with close == 0); the arguments are left alone."""
+    delta (B,), not_close = the number of agents with close == 0); the arguments are left alone.  With ``iz`` in
+    ``prm`` (cmpc_lin3_publish_dev) the buffers are x 3 and new[k] has z[k nxe + iz] as its third entry."""
     z, traj_all = np.asarray(z, np.float64), np.asarray(traj_all, np.float64)
     ix, iy, nxe, off = int(prm["ix"]), int(prm["iy"]), nx + ns, int(self_offset)
+    pd = 3 if "iz" in prm else 2
+    if pd == 3:
+        _pos3(prm, nx)
     if z.ndim != 2 or z.shape[1] != nxe * (N + 1) + 2 * nu * N or traj_all.ndim != 3 or \
-            traj_all.shape[1:] != (N + 1, 2) or not (0 <= off and off + z.shape[0] <= traj_all.shape[0]) or \
+            traj_all.shape[1:] != (N + 1, pd) or not (0 <= off and off + z.shape[0] <= traj_all.shape[0]) or \
             not (0 <= ix < nx and 0 <= iy < nx and ix != iy) or not (atol >= 0 and rtol >= 0):
-        raise ValueError("lin_publish: z (B, (nx+ns)(N+1) + 2 nu N), traj_all (n_total >= self_offset + B, N+1, 2), "
+        raise ValueError(f"lin_publish: z (B, (nx+ns)(N+1) + 2 nu N), traj_all (n_total >= self_offset + B, N+1, {pd}), "
                          "ix != iy in [0, nx), atol, rtol >= 0")
     B = z.shape[0]
     prev = traj_all[off:off + B]
     ok = np.isfinite(z).all(axis=1)
     xi = z[:, :nxe * (N + 1)].reshape(B, N + 1, nxe)
-    new = np.stack([xi[:, :, ix], xi[:, :, iy]], axis=-1)
+    new = _positions(prm, xi)
     traj_local = np.where(ok[:, None, None], new, prev)
     with np.errstate(invalid="ignore", over="ignore"):
         d = np.abs(prev - traj_local).reshape(B, -1)
@@ -309,6 +389,47 @@ def lin_of_di(scen, rows=None):
     return dict(prm=dict(ix=0, iy=1, min_dist=p["min_dist"], wq=p["wq"]),
                 own=dict(qlin_own=qlin_own, C_own=C_own, h_own=h_own), nbr=np.asarray(scen.nbr)[sl], traj=scen.traj,
                 self_offset=sl.start or 0)
+
+
+def rollout3(x0, N, dim=3, dt=DT):
+    """The constant-velocity rollout of 3-D double-integrator states ``x0`` (n, 2 dim), dim >= 3: (n, N+1, 3)
+    positions x0[:, c] + k dt x0[:, dim + c], c = 0, 1, 2 (``make_di``'s rollout with the third column)."""
+    x0 = np.asarray(x0, np.float64)
+    k = np.arange(N + 1)[None, :]
+    return np.stack([x0[:, c:c + 1] + k * dt * x0[:, dim + c:dim + c + 1] for c in range(3)], axis=-1)
+
+
+def lin3_of_di(scen, alt, rows=None):
+    """A 3-D ``DIScenario`` (``dim == 3``) in the linear-model family with 3-D positions (cmpc_lin3_*):
+    ``lin_of_di``'s dict with prm["iz"] = 2, ``x0`` = the scenario's states with column 2 (the altitude) set to
+    ``alt`` (a scalar or (n,)), and ``traj`` = their constant-velocity rollout with three columns (n, N+1, 3).
+    With one altitude for everybody the rows and the cost are ``lin_of_di``'s, bit for bit."""
+    if scen.dim != 3:
+        raise ValueError("lin3_of_di: a scenario with dim == 3")
+    lin = lin_of_di(scen, rows)
+    x0 = np.array(scen.x0, np.float64)
+    x0[:, 2] = alt
+    lin["prm"]["iz"] = 2
+    lin.update(x0=x0, traj=rollout3(x0, scen.N, scen.dim))
+    return lin
+
+
+def make_stacked(n_agents, N, nb=2, gap=0.6):
+    """A population the planar rule cannot separate: ``make_di(n_agents, N, nb, 3)`` with every odd agent over the
+    even agent before it (its ground position, velocity and lane) at altitude ``gap``, the even ones at 0 — pairs
+    on one ground point, ``gap`` apart.  ``traj`` is the 3-column constant-velocity rollout and ``nbr`` the 3-D
+    selection on window (0, 0).  Returns dict(shared, prm, own, A, B, x0, u_prev, nbr, traj) in the 3-D family
+    (prm has ``iz``): the arguments of ``rounds.LinRoundsHandle``."""
+    if n_agents < 2 or n_agents % 2:
+        raise ValueError("make_stacked: an even number of agents")
+    sc = make_di(n_agents, N, nb, 3)
+    i = np.arange(n_agents)
+    below = i - i % 2
+    sc.x0 = sc.x0[below].copy()
+    sc.lane = sc.lane[below].copy()
+    lin = lin3_of_di(sc, gap * (i % 2))
+    return dict(shared=sc.shared, prm=lin["prm"], own=lin["own"], A=sc.A, B=sc.B, x0=lin["x0"], u_prev=sc.u_prev,
+                nbr=select_neighbours(lin["traj"], nb), traj=lin["traj"])
 
 
 TABLE_HOLD, TABLE_PERIODIC = 0, 1   # CMPC_TABLE_HOLD, CMPC_TABLE_PERIODIC

@@ -687,8 +687,9 @@ int cmpc_lpv_gather_dev(cmpc_ctx* ctx, const cmpc_di_dims* d, const int* nbr, co
     return CMPC_OK;
 }
 
-int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* traj_all, int* nbr, double* dist2,
-                        void* stream) {
+// cmpc_nbr_select_dev (pos_dim 2) and cmpc_nbr_select3_dev (3): the same rules, the kernel of the buffer's width
+static int nbr_select(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* traj_all, int* nbr, double* dist2,
+                      void* stream, int pos_dim) {
     if (!ctx) return CMPC_ERR_ARG;
     if (!d || !traj_all) return fail(ctx, CMPC_ERR_ARG, "null argument");
     if (d->batch < 0 || d->N < 1 || d->nb < 0 || d->nb > CMPC_MAX_MC - 4 || d->nb >= d->n_total)
@@ -701,8 +702,21 @@ int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* tra
     int rc = set_device(ctx);
     if (rc != CMPC_OK) return rc;
     const cmpc::NbrConst c{d->batch, d->N, d->nb, d->self_offset, d->n_total, d->k0, d->k1};
-    HIP_TRY(cmpc::nbr_select_launch(c, traj_all, nbr, dist2, (hipStream_t)stream));
+    if (pos_dim == 3)
+        HIP_TRY(cmpc::nbr_select3_launch(c, traj_all, nbr, dist2, (hipStream_t)stream));
+    else
+        HIP_TRY(cmpc::nbr_select_launch(c, traj_all, nbr, dist2, (hipStream_t)stream));
     return CMPC_OK;
+}
+
+int cmpc_nbr_select_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* traj_all, int* nbr, double* dist2,
+                        void* stream) {
+    return nbr_select(ctx, d, traj_all, nbr, dist2, stream, 2);
+}
+
+int cmpc_nbr_select3_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* d, const double* traj_all, int* nbr, double* dist2,
+                         void* stream) {
+    return nbr_select(ctx, d, traj_all, nbr, dist2, stream, 3);
 }
 
 int cmpc_order_by_iters_dev(cmpc_ctx* ctx, int batch, const int* iters, int* order, void* stream) {
@@ -923,13 +937,21 @@ int cmpc_di_advance_dev(cmpc_ctx* ctx, const cmpc_di_params* prm, const cmpc_di_
     return CMPC_OK;
 }
 
-static bool lin_own_ok(const cmpc_lin_dims* d, const int* nbr, const cmpc_lin_own* own) {
+}  // extern "C"
+
+// The linear-model family's device entries, one body for the planar rule (Prm = cmpc_lin_params: cmpc_lin_*) and
+// the 3-D one (cmpc_lin3_params: cmpc_lin3_*).  lin_const (ctx.h) applies the position rules of either; the
+// launches pick the kernels by the position dimension it leaves in LinConst.
+namespace {
+
+bool lin_own_ok(const cmpc_lin_dims* d, const int* nbr, const cmpc_lin_own* own) {
     if (!own || !own->qlin_own) return false;
     if (d && d->mo > 0 && (!own->C_own || !own->h_own)) return false;
     return !(d && d->nb > 0 && !nbr);
 }
 
-int cmpc_lin_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+template <class Prm>
+int lin_build_dev_t(cmpc_ctx* ctx, const Prm* prm, const cmpc_lin_dims* d, const int* nbr,
                        const cmpc_lin_own* own, const double* traj_all, double* qlin, double* C, double* h,
                        void* stream) {
     if (!ctx) return CMPC_ERR_ARG;
@@ -944,7 +966,8 @@ int cmpc_lin_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin
     return CMPC_OK;
 }
 
-int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+template <class Prm>
+int lin_advance_dev_t(cmpc_ctx* ctx, const Prm* prm, const cmpc_lin_dims* d, int ns, int nu,
                          const double* z, double* x0, double* u_prev, double* traj_local, void* stream) {
     if (!ctx) return CMPC_ERR_ARG;
     if (!z || !x0 || !u_prev || !traj_local) return fail(ctx, CMPC_ERR_ARG, "null argument");
@@ -959,7 +982,8 @@ int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_l
     return CMPC_OK;
 }
 
-int cmpc_lin_publish_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+template <class Prm>
+int lin_publish_dev_t(cmpc_ctx* ctx, const Prm* prm, const cmpc_lin_dims* d, int ns, int nu,
                          const double* z, const double* traj_all, double atol, double rtol, double* traj_local,
                          int* close, double* delta, int* not_close, void* stream) {
     if (!ctx) return CMPC_ERR_ARG;
@@ -980,7 +1004,7 @@ int cmpc_lin_publish_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_l
 // What cmpc_lin_round_dev and cmpc_lin_table_round_dev check after their own rules: the two dims structs describe
 // the same agents, and every argument rule of the solver before the first launch (cmpc_solve_mpc_batch_dev
 // repeats them).
-static int lin_round_check(cmpc_ctx* ctx, const cmpc_lin_dims* d, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+int lin_round_check(cmpc_ctx* ctx, const cmpc_lin_dims* d, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                            const cmpc_opts* opts) {
     if (dims->batch != d->batch || dims->N != d->N || dims->nx != d->nx || dims->mc != d->mo + d->nb)
         return fail(ctx, CMPC_ERR_ARG, "linear-model and solver dimensions differ");
@@ -995,7 +1019,7 @@ static int lin_round_check(cmpc_ctx* ctx, const cmpc_lin_dims* d, const cmpc_mpc
 }
 
 // ... and what they run after their build: the solve, then the advance into data->x0 / u_prev and traj_local
-static int lin_solve_advance(cmpc_ctx* ctx, const cmpc::LinConst& c, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
+int lin_solve_advance(cmpc_ctx* ctx, const cmpc::LinConst& c, const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w,
                              const cmpc_mpc_data* in, const cmpc_mpc_out* out, const cmpc_opts* opts, double* traj_local,
                              void* stream) {
     const int rc = cmpc_solve_mpc_batch_dev(ctx, dims, w, in, out, opts, stream);
@@ -1005,7 +1029,8 @@ static int lin_solve_advance(cmpc_ctx* ctx, const cmpc::LinConst& c, const cmpc_
     return CMPC_OK;
 }
 
-int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+template <class Prm>
+int lin_round_dev_t(cmpc_ctx* ctx, const Prm* prm, const cmpc_lin_dims* d, const int* nbr,
                        const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* dims,
                        const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
                        const cmpc_opts* opts, double* traj_local, void* stream) {
@@ -1027,7 +1052,7 @@ int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin
 }
 
 // the stage-table rules of cmpc_lin_table_build_dev / _round_dev (d has passed lin_const); no device call
-static int lin_table_const(cmpc_ctx* ctx, const cmpc_lin_dims* d, int nu, const cmpc_lin_table_dims* td,
+int lin_table_const(cmpc_ctx* ctx, const cmpc_lin_dims* d, int nu, const cmpc_lin_table_dims* td,
                            const cmpc_lin_table* tab, int t, cmpc::LinTableConst* tc) {
     if (td->T < 1 || (td->mode != CMPC_TABLE_HOLD && td->mode != CMPC_TABLE_PERIODIC))
         return fail(ctx, CMPC_ERR_ARG, "bad stage table (T >= 1, mode CMPC_TABLE_HOLD or CMPC_TABLE_PERIODIC)");
@@ -1039,7 +1064,8 @@ static int lin_table_const(cmpc_ctx* ctx, const cmpc_lin_dims* d, int nu, const 
     return CMPC_OK;
 }
 
-int cmpc_lin_table_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int nu,
+template <class Prm>
+int lin_table_build_dev_t(cmpc_ctx* ctx, const Prm* prm, const cmpc_lin_dims* d, int nu,
                              const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const int* nbr,
                              const double* traj_all, double* A, double* B, double* qlin, double* C, double* h,
                              void* stream) {
@@ -1058,7 +1084,8 @@ int cmpc_lin_table_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cm
     return CMPC_OK;
 }
 
-int cmpc_lin_table_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+template <class Prm>
+int lin_table_round_dev_t(cmpc_ctx* ctx, const Prm* prm, const cmpc_lin_dims* d, const int* nbr,
                              const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const double* traj_all,
                              const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
                              const cmpc_mpc_out* out, const cmpc_opts* opts, double* traj_local, void* stream) {
@@ -1080,6 +1107,80 @@ int cmpc_lin_table_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cm
                                const_cast<double*>(in->h)};
     HIP_TRY(cmpc::lin_table_build_launch(c, tc, p, d->batch, s));
     return lin_solve_advance(ctx, c, dims, w, in, out, opts, traj_local, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmpc_lin_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                       const cmpc_lin_own* own, const double* traj_all, double* qlin, double* C, double* h,
+                       void* stream) {
+    return lin_build_dev_t(ctx, prm, d, nbr, own, traj_all, qlin, C, h, stream);
+}
+int cmpc_lin3_build_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                        const cmpc_lin_own* own, const double* traj_all, double* qlin, double* C, double* h,
+                        void* stream) {
+    return lin_build_dev_t(ctx, prm, d, nbr, own, traj_all, qlin, C, h, stream);
+}
+
+int cmpc_lin_advance_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+                         const double* z, double* x0, double* u_prev, double* traj_local, void* stream) {
+    return lin_advance_dev_t(ctx, prm, d, ns, nu, z, x0, u_prev, traj_local, stream);
+}
+int cmpc_lin3_advance_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+                          const double* z, double* x0, double* u_prev, double* traj_local, void* stream) {
+    return lin_advance_dev_t(ctx, prm, d, ns, nu, z, x0, u_prev, traj_local, stream);
+}
+
+int cmpc_lin_publish_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+                         const double* z, const double* traj_all, double atol, double rtol, double* traj_local,
+                         int* close, double* delta, int* not_close, void* stream) {
+    return lin_publish_dev_t(ctx, prm, d, ns, nu, z, traj_all, atol, rtol, traj_local, close, delta, not_close, stream);
+}
+int cmpc_lin3_publish_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, int ns, int nu,
+                          const double* z, const double* traj_all, double atol, double rtol, double* traj_local,
+                          int* close, double* delta, int* not_close, void* stream) {
+    return lin_publish_dev_t(ctx, prm, d, ns, nu, z, traj_all, atol, rtol, traj_local, close, delta, not_close, stream);
+}
+
+int cmpc_lin_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                       const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* dims,
+                       const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
+                       const cmpc_opts* opts, double* traj_local, void* stream) {
+    return lin_round_dev_t(ctx, prm, d, nbr, own, traj_all, dims, w, in, out, opts, traj_local, stream);
+}
+int cmpc_lin3_round_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                        const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* dims,
+                        const cmpc_mpc_weights* w, const cmpc_mpc_data* in, const cmpc_mpc_out* out,
+                        const cmpc_opts* opts, double* traj_local, void* stream) {
+    return lin_round_dev_t(ctx, prm, d, nbr, own, traj_all, dims, w, in, out, opts, traj_local, stream);
+}
+
+int cmpc_lin_table_build_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, int nu,
+                             const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const int* nbr,
+                             const double* traj_all, double* A, double* B, double* qlin, double* C, double* h,
+                             void* stream) {
+    return lin_table_build_dev_t(ctx, prm, d, nu, td, tab, t, nbr, traj_all, A, B, qlin, C, h, stream);
+}
+int cmpc_lin3_table_build_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, int nu,
+                              const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const int* nbr,
+                              const double* traj_all, double* A, double* B, double* qlin, double* C, double* h,
+                              void* stream) {
+    return lin_table_build_dev_t(ctx, prm, d, nu, td, tab, t, nbr, traj_all, A, B, qlin, C, h, stream);
+}
+
+int cmpc_lin_table_round_dev(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                             const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const double* traj_all,
+                             const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                             const cmpc_mpc_out* out, const cmpc_opts* opts, double* traj_local, void* stream) {
+    return lin_table_round_dev_t(ctx, prm, d, nbr, td, tab, t, traj_all, dims, w, in, out, opts, traj_local, stream);
+}
+int cmpc_lin3_table_round_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, const int* nbr,
+                              const cmpc_lin_table_dims* td, const cmpc_lin_table* tab, int t, const double* traj_all,
+                              const cmpc_mpc_dims* dims, const cmpc_mpc_weights* w, const cmpc_mpc_data* in,
+                              const cmpc_mpc_out* out, const cmpc_opts* opts, double* traj_local, void* stream) {
+    return lin_table_round_dev_t(ctx, prm, d, nbr, td, tab, t, traj_all, dims, w, in, out, opts, traj_local, stream);
 }
 
 int cmpc_solve_qp_batch(cmpc_ctx* ctx, const cmpc_qp_dims* d, const cmpc_qp_data* in, const cmpc_qp_out* out,

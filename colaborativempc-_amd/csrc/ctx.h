@@ -37,7 +37,19 @@ inline int lin_const(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_lin_d
         return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (1 <= nx <= 12, position columns ix != iy in [0, nx))");
     if (d->N < 1 || d->nb < 0 || d->mo < 0 || d->mo + d->nb > CMPC_MAX_MC || d->batch < 0 || d->self_offset < 0)
         return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (N >= 1, mo + nb <= 16, batch >= 0, self_offset >= 0)");
-    *c = cmpc::LinConst{d->N, d->nb, d->nx, d->mo, prm->ix, prm->iy, d->self_offset, prm->min_dist, prm->wq};
+    *c = cmpc::LinConst{d->N, d->nb, d->nx, d->mo, prm->ix, prm->iy, d->self_offset, -1, prm->min_dist, prm->wq};
+    return CMPC_OK;
+}
+
+// ... and of its 3-D variant (cmpc_lin3_*): the planar rules, and a third position column apart from both
+inline int lin_const(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* d, cmpc::LinConst* c) {
+    if (!prm) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    const cmpc_lin_params planar{prm->ix, prm->iy, prm->min_dist, prm->wq};
+    const int rc = lin_const(ctx, &planar, d, c);
+    if (rc != CMPC_OK) return rc;
+    if (prm->iz < 0 || prm->iz >= d->nx || prm->iz == prm->ix || prm->iz == prm->iy)
+        return fail(ctx, CMPC_ERR_ARG, "bad linear-model dimensions (position columns ix, iy, iz pairwise different in [0, nx))");
+    c->iz = prm->iz;
     return CMPC_OK;
 }
 

@@ -317,6 +317,8 @@ struct NbrConst {
     int batch, N, nb, self_offset, n_total, k0, k1;
 };
 hipError_t nbr_select_launch(const NbrConst& c, const double* traj_all, int* nbr, double* dist2, hipStream_t s);
+// the same selection on 3-D positions (cmpc_nbr_select3_dev): traj_all is n_total x (N+1) x 3
+hipError_t nbr_select3_launch(const NbrConst& c, const double* traj_all, int* nbr, double* dist2, hipStream_t s);
 
 // Launch order (order.hip): order <- the agents by descending min(max(iters, 0), 65535), ties by ascending
 // index; tmp: batch x 8 bytes of device scratch.  One workgroup; nothing is launched for batch <= 0
@@ -357,11 +359,15 @@ hipError_t di_advance_launch(const DiConst& c, const double* z, double* x0, doub
                              hipStream_t s);
 
 // Rounds for any linear agent model (lin_build.hip): own rows / cost copied, nb planes and the coverage term
-// appended (the arithmetic of di_rows.h); the advance skips an agent whose z is not finite.
+// appended (the arithmetic of di_rows.h); the advance skips an agent whose z is not finite.  The position is the
+// state columns ix, iy (iz < 0: the planar rule, trajectories x 2) or ix, iy, iz (cmpc_lin3_*: trajectories x 3);
+// the launches below pick the kernels' position dimension by it.
 
 struct LinConst {
     int N, nb, nx, mo, ix, iy, self_offset;
+    int iz;
     double min_dist, wq;
+    int pos_dim() const { return iz < 0 ? 2 : 3; }
 };
 
 struct LinPtrs {

@@ -12,6 +12,8 @@
 //   LIN, a consensus step (cmpc_lin_rounds_step_consensus): [cmpc_nbr_select_dev ->] inner rounds of
 //        cmpc_lin[_table]_build_dev -> cmpc_solve_mpc_batch_dev -> cmpc_lin_publish_dev -> exchange -> 4-byte
 //        read-back, until the published positions agree -> cmpc_lin_advance_dev
+//   LIN with 3-D positions (cmpc_lin_rounds_create3 / _create_table3): the same chains with cmpc_lin3_* for
+//        cmpc_lin_* and cmpc_nbr_select3_dev for cmpc_nbr_select_dev, on exchange rows of 3 (N + 1) doubles
 // where the exchange is a device copy (one rank), the RCCL all-gather of the context's communicator
 // (cmpc_allgather_trajectories), or the host's (CMPC_ROUNDS_HOST_EXCHANGE).  With the log on
 // (cmpc_*_rounds_log_enable) a round ends with cmpc_round_log_dev [-> cmpc_nbr_select_dev, nb = 1] into the
@@ -98,7 +100,13 @@ struct RoundsCore {
 
     bool sharded() const { return d.batch != d.n_total; }
     bool host_exchange() const { return d.flags & CMPC_ROUNDS_HOST_EXCHANGE; }
-    size_t traj_row() const { return 2 * (size_t)(d.N + 1); }  // doubles of one agent's predicted positions
+    int pos_dim = 2;  // coordinates of a position: 3 on a handle of cmpc_lin_rounds_create3 / _create_table3
+    size_t traj_row() const { return (size_t)pos_dim * (d.N + 1); }  // doubles of one agent's predicted positions
+    // cmpc_nbr_select_dev on the exchange buffer, by its width
+    int select(const cmpc_nbr_dims* sd, int* nbr_out, double* dist2, hipStream_t s) const {
+        return pos_dim == 3 ? cmpc_nbr_select3_dev(ctx, sd, traj_all, nbr_out, dist2, s)
+                            : cmpc_nbr_select_dev(ctx, sd, traj_all, nbr_out, dist2, s);
+    }
 };
 
 struct cmpc_lpv_rounds : RoundsCore {
@@ -132,6 +140,7 @@ struct cmpc_di_rounds : SolverRounds {
 
 struct cmpc_lin_rounds : SolverRounds {
     cmpc_lin_params prm{};
+    cmpc_lin3_params prm3{};  // pos_dim == 3: the rounds call the cmpc_lin3_* entries with it
     int mo = 0;
     // the own data, only read by the rounds: the fixed window (N + 1 / N / N stages, uploaded once), or the qlin /
     // C / h rows of a stage table (T stages each)
@@ -214,7 +223,7 @@ bool stages_lti(const double* a, size_t batch, size_t N, size_t per) {
 int reselect(RoundsCore* h, hipStream_t s) {
     if (!(h->d.flags & CMPC_ROUNDS_RESELECT) || h->d.nb == 0) return CMPC_OK;
     const cmpc_nbr_dims sd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->d.n_total, 0, 0};
-    return cmpc_nbr_select_dev(h->ctx, &sd, h->traj_all, h->nbr, nullptr, s);
+    return h->select(&sd, h->nbr, nullptr, s);
 }
 
 // traj_local -> every rank's traj_all; with the host's exchange (sharded) nothing: the host does it between steps
@@ -387,7 +396,7 @@ int log_round(RoundsCore* h, int r, const double* z, const double* kkt, const in
                            lg->kkt + row, lg->iters + row, lg->status + row};
     int rc = cmpc_round_log_dev(h->ctx, &lg->d, z, kkt, iters, status, &dst, s);
     if (rc == CMPC_OK && (lg->flags & CMPC_LOG_SEPARATION))
-        rc = cmpc_nbr_select_dev(h->ctx, &lg->sel, h->traj_all, lg->nearest + row, lg->sep2 + row, s);
+        rc = h->select(&lg->sel, lg->nearest + row, lg->sep2 + row, s);
     if (rc != CMPC_OK) return rc;
     if (r != lg->end) lg->first = r;  // a round in between went unlogged (its exchange failed): the log restarts here
     lg->end = r + 1;
@@ -561,7 +570,16 @@ struct LinInit {
     const double* traj;
 };
 
-int lin_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights* w, const cmpc_lin_rounds_dims* dims,
+void set_position(cmpc_lin_rounds* h, const cmpc_lin_params& prm) { h->prm = prm; }
+void set_position(cmpc_lin_rounds* h, const cmpc_lin3_params& prm) {
+    h->prm = cmpc_lin_params{prm.ix, prm.iy, prm.min_dist, prm.wq};
+    h->prm3 = prm;
+    h->pos_dim = 3;
+}
+
+// Prm: cmpc_lin_params, or cmpc_lin3_params (in.traj is then n_total x (N+1) x 3)
+template <class Prm>
+int lin_create(cmpc_ctx* ctx, const Prm* prm, const cmpc_mpc_weights* w, const cmpc_lin_rounds_dims* dims,
                const LinInit& in, bool table, const cmpc_opts* opts, cmpc_lin_rounds** out) {
     const cmpc_lpv_rounds_dims d{dims->n_total, dims->batch, dims->self_offset, dims->N, dims->nb, dims->flags};
     const cmpc_lin_dims ld{d.batch, d.N, d.nb, d.self_offset, dims->nx, dims->mo};
@@ -585,7 +603,7 @@ int lin_create(cmpc_ctx* ctx, const cmpc_lin_params* prm, const cmpc_mpc_weights
 
     auto* h = new cmpc_lin_rounds();
     core_init(h, ctx, d, opts);
-    h->prm = *prm;
+    set_position(h, *prm);
     h->mo = dims->mo;
     h->history = std::max(dims->history, 1);
     if (table) {
@@ -994,6 +1012,34 @@ int cmpc_lin_rounds_create_table(cmpc_ctx* ctx, const cmpc_lin_params* prm, cons
     return lin_create(ctx, prm, w, dims, li, true, opts, out);
 }
 
+// ... and both with 3-D positions (include/cmpc.h, cmpc_lin3_*): the same handle, its exchange rows x 3
+int cmpc_lin_rounds_create3(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_mpc_weights* w,
+                            const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_init* in, const cmpc_opts* opts,
+                            cmpc_lin_rounds** out) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    *out = nullptr;
+    const LinInit li{0, 0, 0, in->A, in->B, in->qlin_own, in->C_own, in->h_own, in->x0, in->u_prev, in->nbr, in->traj};
+    return lin_create(ctx, prm, w, dims, li, false, opts, out);
+}
+
+int cmpc_lin_rounds_create_table3(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_mpc_weights* w,
+                                  const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_table_init* in,
+                                  const cmpc_opts* opts, cmpc_lin_rounds** out) {
+    if (!ctx) return CMPC_ERR_ARG;
+    if (!out || !prm || !w || !dims || !in) return fail(ctx, CMPC_ERR_ARG, "null argument");
+    *out = nullptr;
+    const LinInit li{in->T, in->mode, in->t0, in->A, in->B, in->qlin, in->C, in->h, in->x0, in->u_prev, in->nbr, in->traj};
+    return lin_create(ctx, prm, w, dims, li, true, opts, out);
+}
+
+int cmpc_lin_rounds_pos_dim(cmpc_lin_rounds* h, int* pos_dim) {
+    if (!h) return CMPC_ERR_ARG;
+    if (!pos_dim) return fail(h->ctx, CMPC_ERR_ARG, "null output");
+    *pos_dim = h->pos_dim;
+    return CMPC_OK;
+}
+
 int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
     if (!h) return CMPC_ERR_ARG;
     const cmpc_lin_dims rd{h->d.batch, h->d.N, h->d.nb, h->d.self_offset, h->md.nx, h->mo};
@@ -1002,9 +1048,14 @@ int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
         const cmpc_lin_table tab{h->A_tab, h->B_tab, h->qlin_own, h->C_own, h->h_own};
         return step_rounds(h, rounds, rounds_done, "cmpc_lin_rounds_step: log event",
                            [&](const cmpc_mpc_data* din, const cmpc_mpc_out* dout, hipStream_t s) {
-                               const int rc = cmpc_lin_table_round_dev(h->ctx, &h->prm, &rd, h->nbr, &td, &tab, h->t,
-                                                                       h->traj_all, &h->md, &h->w, din, dout, &h->opts,
-                                                                       h->traj_local, s);
+                               const int rc =
+                                   h->pos_dim == 3
+                                       ? cmpc_lin3_table_round_dev(h->ctx, &h->prm3, &rd, h->nbr, &td, &tab, h->t,
+                                                                   h->traj_all, &h->md, &h->w, din, dout, &h->opts,
+                                                                   h->traj_local, s)
+                                       : cmpc_lin_table_round_dev(h->ctx, &h->prm, &rd, h->nbr, &td, &tab, h->t,
+                                                                  h->traj_all, &h->md, &h->w, din, dout, &h->opts,
+                                                                  h->traj_local, s);
                                if (rc == CMPC_OK)
                                    h->t = h->mode == CMPC_TABLE_PERIODIC ? (h->t + 1) % h->T : std::min(h->t + 1, h->T - 1);
                                return rc;
@@ -1013,8 +1064,11 @@ int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
     const cmpc_lin_own own{h->qlin_own, h->C_own, h->h_own};
     return step_rounds(h, rounds, rounds_done, "cmpc_lin_rounds_step: log event",
                        [&](const cmpc_mpc_data* din, const cmpc_mpc_out* dout, hipStream_t s) {
-                           return cmpc_lin_round_dev(h->ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, &h->md, &h->w,
-                                                     din, dout, &h->opts, h->traj_local, s);
+                           return h->pos_dim == 3
+                                      ? cmpc_lin3_round_dev(h->ctx, &h->prm3, &rd, h->nbr, &own, h->traj_all, &h->md,
+                                                            &h->w, din, dout, &h->opts, h->traj_local, s)
+                                      : cmpc_lin_round_dev(h->ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, &h->md,
+                                                           &h->w, din, dout, &h->opts, h->traj_local, s);
                        });
 }
 
@@ -1026,7 +1080,7 @@ int cmpc_lin_rounds_step(cmpc_lin_rounds* h, int rounds, int* rounds_done) {
 static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hipStream_t s, int* inner) {
     cmpc_ctx* ctx = h->ctx;
     *inner = 0;
-    const bool lpt = h->d.flags & CMPC_ROUNDS_LPT;
+    const bool lpt = h->d.flags & CMPC_ROUNDS_LPT, p3 = h->pos_dim == 3;  // p3: the cmpc_lin3_* entries
     const int round = h->rounds_done;
     const size_t slot = (size_t)(round % h->history) * h->d.batch;  // this step's row of the history ring
     const cmpc_mpc_data din{h->A, h->B, h->x0, h->u_prev, h->qlin, h->C, h->h};
@@ -1042,9 +1096,14 @@ static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hip
     int j = 0;
     for (;;) {
         ++j;
-        rc = h->T ? cmpc_lin_table_build_dev(ctx, &h->prm, &rd, h->md.nu, &td, &tab, h->t, h->nbr, h->traj_all, h->A,
-                                             h->B, h->qlin, h->C, h->h, s)
-                  : cmpc_lin_build_dev(ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, h->qlin, h->C, h->h, s);
+        if (p3)
+            rc = h->T ? cmpc_lin3_table_build_dev(ctx, &h->prm3, &rd, h->md.nu, &td, &tab, h->t, h->nbr, h->traj_all,
+                                                  h->A, h->B, h->qlin, h->C, h->h, s)
+                      : cmpc_lin3_build_dev(ctx, &h->prm3, &rd, h->nbr, &own, h->traj_all, h->qlin, h->C, h->h, s);
+        else
+            rc = h->T ? cmpc_lin_table_build_dev(ctx, &h->prm, &rd, h->md.nu, &td, &tab, h->t, h->nbr, h->traj_all,
+                                                 h->A, h->B, h->qlin, h->C, h->h, s)
+                      : cmpc_lin_build_dev(ctx, &h->prm, &rd, h->nbr, &own, h->traj_all, h->qlin, h->C, h->h, s);
         h->opts.order = (lpt && (round > 0 || j > 1)) ? h->order : nullptr;
         if (rc == CMPC_OK) rc = cmpc_solve_mpc_batch_dev(ctx, &h->md, &h->w, &din, &dout, &h->opts, s);
         if (rc != CMPC_OK) {
@@ -1054,9 +1113,11 @@ static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hip
         // the next solve's launch order, stream-ordered after this one
         if (lpt && (rc = cmpc_order_by_iters_dev(ctx, h->d.batch, h->iters + slot, h->order, s)) != CMPC_OK) return rc;
         HIP_TRY(hipMemsetAsync(h->counts, 0, sizeof(int), s));
-        if ((rc = cmpc_lin_publish_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->traj_all, co.atol, co.rtol,
-                                       h->traj_local, h->close, h->delta, h->counts, s)) != CMPC_OK)
-            return rc;
+        rc = p3 ? cmpc_lin3_publish_dev(ctx, &h->prm3, &rd, h->md.ns, h->md.nu, h->z, h->traj_all, co.atol, co.rtol,
+                                        h->traj_local, h->close, h->delta, h->counts, s)
+                : cmpc_lin_publish_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->traj_all, co.atol, co.rtol,
+                                       h->traj_local, h->close, h->delta, h->counts, s);
+        if (rc != CMPC_OK) return rc;
         if ((rc = exchange(h, s)) != CMPC_OK) return rc;
         // the node's count, not this rank's: every rank must leave the loop after the same inner round (a rank
         // that left alone would keep the others waiting in the next all-gather)
@@ -1068,9 +1129,9 @@ static int consensus_step(cmpc_lin_rounds* h, const cmpc_consensus_opts& co, hip
     }
     HIP_TRY(log_mark(h->log, round, 1, s));
     // x0, u_prev from the final z; traj_local again, with the values the last inner round exchanged
-    if ((rc = cmpc_lin_advance_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->x0, h->u_prev, h->traj_local, s)) !=
-        CMPC_OK)
-        return rc;
+    rc = p3 ? cmpc_lin3_advance_dev(ctx, &h->prm3, &rd, h->md.ns, h->md.nu, h->z, h->x0, h->u_prev, h->traj_local, s)
+            : cmpc_lin_advance_dev(ctx, &h->prm, &rd, h->md.ns, h->md.nu, h->z, h->x0, h->u_prev, h->traj_local, s);
+    if (rc != CMPC_OK) return rc;
     ++h->rounds_done;
     if (h->T) h->t = h->mode == CMPC_TABLE_PERIODIC ? (h->t + 1) % h->T : std::min(h->t + 1, h->T - 1);
     h->trace = std::move(loop.trace);

@@ -61,7 +61,11 @@ extern "C" {
                                 cmpc_lin_publish_dev, cmpc_consensus_opts, cmpc_consensus_out,
                                 cmpc_lin_rounds_step_consensus, cmpc_lin_rounds_consensus_read;
                                 cmpc_lpv_publish_dev, cmpc_lpv_rounds_step_consensus,
-                                cmpc_lpv_rounds_consensus_read */
+                                cmpc_lpv_rounds_consensus_read;
+                                cmpc_lin3_params, cmpc_lin3_build_dev, cmpc_lin3_table_build_dev,
+                                cmpc_lin3_advance_dev, cmpc_lin3_publish_dev, cmpc_lin3_round_dev,
+                                cmpc_lin3_table_round_dev, cmpc_nbr_select3_dev, cmpc_lin_rounds_create3,
+                                cmpc_lin_rounds_create_table3, cmpc_lin_rounds_pos_dim */
 
 /* API error codes */
 #define CMPC_OK 0
@@ -1182,6 +1186,84 @@ typedef struct {    /* HOST pointers, any may be NULL */
 int cmpc_lin_rounds_step_consensus(cmpc_lin_rounds* h, int steps, const cmpc_consensus_opts* co, int* steps_done,
                                    int* inner_total);
 int cmpc_lin_rounds_consensus_read(cmpc_lin_rounds* h, const cmpc_consensus_out* host_out);
+
+/* ------------------------------------------------------------------------
+ * Positions in three dimensions on the linear-model family (cmpc_lin3_*, cmpc_nbr_select3_dev): the coupling of
+ * agents that move in space (the 3-D double integrator: nx = 6, nu = 3).  The position is three state columns ix,
+ * iy, iz, pairwise different and each in [0, nx), and every exchange buffer is x 3: traj_all n_total x (N+1) x 3,
+ * traj_local batch x (N+1) x 3.  Everything that does not touch a position is the planar family's, and each entry
+ * point below has the signature, the launch shape (one wavefront per agent, no LDS, no scratch, stream-ordered,
+ * graph-capturable) and the error rules of its namesake without the 3, with cmpc_lin3_params for cmpc_lin_params.
+ * Every expression is rounded as written (no fma) and sums run left to right; cmpc.scenarios.lin_rows /
+ * lin_advance / lin_publish / select_neighbours with `iz` in prm (a 3-column buffer) are the numpy statements.
+ *
+ * cmpc_lin3_build_dev, cmpc_lin3_table_build_dev: cmpc_lin_build_dev's rule with, for neighbour i of stage k,
+ * e = own[k-1], n = traj_all[j,k-1]:
+ *       dx, dy, dz = n - e;  nrm = sqrt(dx*dx + dy*dy + dz*dz);  ax, ay, az = dx/nrm, dy/nrm, dz/nrm
+ *       bb = -0.5*(ax*(e_x + n_x) + ay*(e_y + n_y) + az*(e_z + n_z))
+ *       C[b,k-1,mo+i,:] = 0 except [ix] = ax, [iy] = ay, [iz] = az;  h[b,k-1,mo+i] = -min_dist/2 - bb
+ *     coverage, from row k:  qx, qy, qz = own[k] - traj_all[j,k];
+ *       wgt = (2*min_dist - sqrt(qx*qx + qy*qy + qz*qz))/nb;  px = px + wq*wgt*ax, py, pz likewise, accumulated
+ *       from 0.0 in neighbour order;  then qlin[b,k,ix] += px, qlin[b,k,iy] += py, qlin[b,k,iz] += pz
+ *   stage 0 gets no coverage term; the own rows and the own cost are copied as in the planar rule.  A neighbour on
+ *   the agent's own 3-D point gives NaN for that agent and that stage only: two agents over one ground point at
+ *   different altitudes have finite rows.  When every position has the same third coordinate, dz = 0 and the rows
+ *   and the cost are the planar builder's, with a zero in column iz.
+ * cmpc_lin3_advance_dev, cmpc_lin3_publish_dev: new[k] = (z[k nxe + ix], z[k nxe + iy], z[k nxe + iz]), 3(N+1)
+ *   entries per agent; the non-finite guard, the allclose test, delta with numpy's max, the atomic count and the
+ *   copy (-0.0 stays -0.0) are cmpc_lin_advance_dev's / cmpc_lin_publish_dev's.
+ * cmpc_lin3_round_dev, cmpc_lin3_table_round_dev: the planar rounds with those builds and that advance.
+ * cmpc_nbr_select3_dev: cmpc_nbr_select_dev with score(g, j) = min over k in [k0, k1] of (dx*dx + dy*dy + dz*dz);
+ *   the NaN, tie-break, self-exclusion and error rules are unchanged.
+ *
+ * cmpc_lin_rounds_create3 / cmpc_lin_rounds_create_table3 are cmpc_lin_rounds_create / _create_table with
+ * cmpc_lin3_params and an x 3 initial buffer (init->traj: n_total x (N+1) x 3).  They return the same
+ * cmpc_lin_rounds, and every other handle function works on it unchanged: _step, _step_consensus,
+ * _consensus_read, _read, _history, _set_state, _get_time, _set_time, _table_write, the log functions, _destroy.
+ * On such a handle _get_traj / _set_traj move 3(N+1) doubles per agent, CMPC_ROUNDS_RESELECT and
+ * CMPC_LOG_SEPARATION run cmpc_nbr_select3_dev (sep2 is the squared 3-D distance), the log's look_col stays ix,
+ * and the exchange (device copy, communicator, host) moves the longer rows.  cmpc_lin_rounds_pos_dim gives 2 or 3.
+ *
+ * CMPC_ERR_ARG: what the planar namesake lists; iz equal to ix or iy; iz outside [0, nx).
+ * ---------------------------------------------------------------------- */
+typedef struct { int ix, iy, iz; double min_dist, wq; } cmpc_lin3_params; /* position = state columns ix, iy, iz */
+
+int cmpc_lin3_build_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* dims,
+                        const int* nbr /* batch x nb, global agent indices */, const cmpc_lin_own* own,
+                        const double* traj_all /* n_total x (N+1) x 3 */, double* qlin /* batch x (N+1) x nx */,
+                        double* C /* batch x N x (mo+nb) x nx */, double* h /* batch x N x (mo+nb) */,
+                        void* hip_stream);
+int cmpc_lin3_advance_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* dims, int ns, int nu,
+                          const double* z /* batch x nz */, double* x0 /* batch x nx */,
+                          double* u_prev /* batch x nu */, double* traj_local /* batch x (N+1) x 3 */,
+                          void* hip_stream);
+int cmpc_lin3_publish_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* dims, int ns, int nu,
+                          const double* z /* batch x nz */, const double* traj_all /* n_total x (N+1) x 3 */,
+                          double atol, double rtol, double* traj_local /* batch x (N+1) x 3 */,
+                          int* close /* batch, may be NULL */, double* delta /* batch, may be NULL */,
+                          int* not_close /* device int, may be NULL */, void* hip_stream);
+int cmpc_lin3_round_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* ldims, const int* nbr,
+                        const cmpc_lin_own* own, const double* traj_all, const cmpc_mpc_dims* mpc_dims,
+                        const cmpc_mpc_weights* w, const cmpc_mpc_data* data, const cmpc_mpc_out* out,
+                        const cmpc_opts* opts, double* traj_local /* batch x (N+1) x 3 */, void* hip_stream);
+int cmpc_lin3_table_build_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* dims, int nu,
+                              const cmpc_lin_table_dims* tdims, const cmpc_lin_table* table, int t, const int* nbr,
+                              const double* traj_all /* n_total x (N+1) x 3 */, double* A, double* B, double* qlin,
+                              double* C, double* h, void* hip_stream);
+int cmpc_lin3_table_round_dev(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_lin_dims* ldims, const int* nbr,
+                              const cmpc_lin_table_dims* tdims, const cmpc_lin_table* table, int t,
+                              const double* traj_all, const cmpc_mpc_dims* mpc_dims, const cmpc_mpc_weights* w,
+                              const cmpc_mpc_data* data, const cmpc_mpc_out* out, const cmpc_opts* opts,
+                              double* traj_local /* batch x (N+1) x 3 */, void* hip_stream);
+int cmpc_nbr_select3_dev(cmpc_ctx* ctx, const cmpc_nbr_dims* dims, const double* traj_all /* n_total x (N+1) x 3 */,
+                         int* nbr /* batch x nb */, double* dist2 /* batch x nb, may be NULL */, void* hip_stream);
+int cmpc_lin_rounds_create3(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_mpc_weights* w,
+                            const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_init* init, const cmpc_opts* opts,
+                            cmpc_lin_rounds** out);
+int cmpc_lin_rounds_create_table3(cmpc_ctx* ctx, const cmpc_lin3_params* prm, const cmpc_mpc_weights* w,
+                                  const cmpc_lin_rounds_dims* dims, const cmpc_lin_rounds_table_init* init,
+                                  const cmpc_opts* opts, cmpc_lin_rounds** out);
+int cmpc_lin_rounds_pos_dim(cmpc_lin_rounds* h, int* pos_dim /* 2, or 3 on a handle of the create3 forms */);
 
 /* ------------------------------------------------------------------------
  * Consensus steps of the reference's LPV agents (cmpc_lpv_rounds_*): the same step on the handle that drives the
